@@ -12,7 +12,12 @@ gather of the per-rank setup.  Under torch.distributed.run (WORLD_SIZE set) this
 one rank; `--gpus N > 1` without it starts the N ranks under torch.distributed.run as a
 child process (before anything touches a GPU) and exits with its code.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--config c5] [--n N]
+A plain run sets up, warms up, times the steps and prints the result line (`cpu_baseline`
+null).  `--full` adds the CPU baselines of SURVEY 8(d), timed on this host after the GPU
+window.  `--dump-outputs DIR` writes what the last timed step left (dump_outputs).
+
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--config c5] [--n N] [--full]
+                       [--dump-outputs DIR]
 """
 from __future__ import annotations
 
@@ -315,7 +320,15 @@ def main():
     ap.add_argument("--cpu-threads", type=int, default=0,
                     help="threads of the optimised CPU baseline (0: every CPU this process may use, within the "
                          "share OMP_NUM_THREADS allots it -- 16 per GPU on the GPU box)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also time the CPU baselines (cpu_baseline in the result line; one rank only): "
+                         "off by default, a plain run does only what its headline figure needs")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU baselines (a plain run never times them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what they computed as DIR/<name>.npy: the per-step "
+                         "loglik and accepted the timed call returned, and the chain state its last step left "
+                         "(labels, centers, sigma)")
     ap.add_argument("--traffic-csv", action="append", default=None,
                     help="rocprofv3 --pmc counter_collection CSV(s) with FETCH_SIZE / WRITE_SIZE of this workload "
                          "(separate passes); default: profiles/r01/pmc_{fetch,write}_<config>.csv when present")
@@ -384,10 +397,11 @@ def main():
     t0 = time.perf_counter()
     if args.record:
         # every iteration saved (burnin 0, thinning 1): its K, labels, centers, sigmas, loglik
+        per_step = []
         for k0 in range(0, args.steps, rec_batch):
-            eng.iterations_record(it + k0, min(rec_batch, args.steps - k0), out=rec_buf)
+            per_step.append(eng.iterations_record(it + k0, min(rec_batch, args.steps - k0), out=rec_buf)[:2])
     else:
-        eng.iterations(it, args.steps)
+        per_step = [eng.iterations(it, args.steps)]
     it += args.steps
     eng.synchronize()
     cuda_sync()
@@ -396,8 +410,12 @@ def main():
     elapsed = D.max(mine)
     ranks = D.gather(dict(setup, ms_per_step=round(1e3 * mine / args.steps, 4)))
     st = eng.stats()
-    c, cen, _ = eng.get_state()
+    c, cen, sig = eng.get_state()
     K = int(cen.shape[0])
+    if args.dump_outputs and rank == 0:
+        acc_steps, ll_steps = (np.concatenate(x) for x in zip(*per_step))
+        dump_outputs(args.dump_outputs, {"loglik": ll_steps, "accepted": acc_steps, "labels": c,
+                                         "centers": cen, "sigma": sig})
 
     value = aggregate(ws, args.steps, elapsed)
     bpp = prepass_bytes_per_point(ds.d, int(ds.attrisize.max()), args.m)
@@ -527,7 +545,7 @@ def main():
         "survey_8d_bytes_per_sweep": survey_sweep_bytes(ds.n, ds.d, args.m),
         "note": "the sweep proves 'stay' from bounds for most points (DESIGN.md 4.3-4.4) and moves the prepass bytes; "
                 "SURVEY 8(d)'s N(D(2+9m)+8) is the direct design's traffic and is not the roofline of this path"}
-    if rank == 0 and ws == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and ws == 1 and not args.no_cpu_baseline:
         # the optimised oracle's threads: --cpu-threads, else this process's CPU share
         # (OMP_NUM_THREADS: 16 per GPU on the GPU box, whose nproc counts the whole host),
         # else every usable CPU -- the source is recorded in the line
@@ -565,6 +583,30 @@ def dry_run(args, ws, rank, local):
                           "ms_per_step": round(1e3 * elapsed / args.steps, 4), "scaling": "weak",
                           "config": {"parallelism": f"replicas{ws}", "ranks": ranks}}), flush=True)
     D.close()
+
+
+DUMP_MAX_BYTES = 48 << 20    # of array data: the files stay under 64 MB in all
+
+
+def dump_outputs(path: str, arrays: dict):
+    """What a caller of the timed path receives, as <path>/<name>.npy (rank 0's chain in a
+    multi-GPU run): the per-step log-likelihoods and accepted counts the timed
+    hdpm_iterations call(s) returned, float64, and the state the last step left --
+    labels (float32: cluster indexes, exact below 2^24), centers and sigma (K x D float64).
+    Whole arrays while they fit 64 MB in all; past that every array keeps a fixed, seeded
+    sample of its flattened elements, in index order (the same elements from run to run)."""
+    os.makedirs(path, exist_ok=True)
+    out = {k: np.ascontiguousarray(a, np.float32 if k == "labels" else np.float64) for k, a in arrays.items()}
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_MAX_BYTES:
+        rng = np.random.Generator(np.random.MT19937(20240611))
+        frac = DUMP_MAX_BYTES / total
+        for k in sorted(out):
+            flat = out[k].reshape(-1)
+            keep = np.sort(rng.choice(flat.size, size=int(flat.size * frac), replace=False))
+            out[k] = flat[keep]
+    for k, a in out.items():
+        np.save(os.path.join(path, k + ".npy"), a)
 
 
 def stats_diff(a, b):

@@ -149,3 +149,28 @@ def test_traffic_from_csv(tmp_path, rows):
     assert bench.prepass_shape(128, 4, 3) == (52, 192, "gather64")
     assert bench.prepass_shape(784, 6, 3) == (436, 3 * 448, "gather448g")
     assert bench.prepass_shape(2100, 2, 3)[2] == "gather128"
+
+
+def test_dump_outputs(tmp_path, monkeypatch):
+    """bench.dump_outputs: whole arrays as float64 (labels float32) while they fit; past the
+    limit a fixed sample of every array, the same elements from call to call."""
+    import numpy as np
+    import bench
+    arrays = {"loglik": np.arange(5) * -1.5, "accepted": np.zeros(5, np.int32), "labels": np.arange(1000, dtype=np.int32),
+              "centers": np.ones((3, 4)), "sigma": np.full((3, 4), 0.25)}
+    bench.dump_outputs(str(tmp_path / "a"), arrays)
+    got = {f[:-4]: np.load(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")}
+    assert sorted(got) == sorted(arrays)
+    for k, a in arrays.items():
+        assert got[k].dtype == (np.float32 if k == "labels" else np.float64)
+        assert got[k].shape == a.shape and np.array_equal(got[k], a)
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 2048)
+    total = sum(a.size * (4 if k == "labels" else 8) for k, a in arrays.items())
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), arrays)
+    b = {f: np.load(tmp_path / "b" / f) for f in os.listdir(tmp_path / "b")}
+    assert sum(a.nbytes for a in b.values()) <= 2048 < total
+    lab = b["labels.npy"]
+    assert 0 < lab.size < 1000 and np.all(np.diff(lab) > 0)        # elements of the labels, in index order
+    for f, a in b.items():
+        assert np.array_equal(a, np.load(tmp_path / "c" / f))

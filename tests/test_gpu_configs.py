@@ -390,3 +390,43 @@ def test_c2_latent_bounds(hd, oracle, lat):
     neal8_steps(eng, oracle, ds, ost, rng, pc, ps, sweeps=4)
     assert eng.stats()["exact_lanes_launches"] > 0
     eng.close()
+
+
+def test_bench_dump_outputs(hd, tmp_path):
+    """`bench.py --dump-outputs DIR` (plain run, C2): the files hold what the timed call
+    returned (per-step loglik / accepted) and the state its last step left, bit for bit what
+    the same calls give in this process (same data seed, chain seed 1 + rank); a plain run
+    times no CPU baseline."""
+    import json
+    import subprocess
+    import sys
+    from split_and_merge_gibbs_sampling_amd.data import config
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    warm, timed = 2, 5
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--config", "c2", "--steps",
+                        str(timed), "--warmup", str(warm), "--dump-outputs", str(tmp_path / "out")],
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]
+    line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert line["steps"] == timed and line["ms_per_step"] > 0 and line["cpu_baseline"] is None
+    got = {f[:-4]: np.load(tmp_path / "out" / f) for f in sorted(os.listdir(tmp_path / "out"))}
+    assert sorted(got) == ["accepted", "centers", "labels", "loglik", "sigma"]
+    assert got["labels"].dtype == np.float32 and all(got[k].dtype == np.float64 for k in got if k != "labels")
+    assert sum(a.nbytes for a in got.values()) <= 64e6
+
+    ds = config("c2")
+    eng = hd.Engine(0)
+    eng.set_data(ds.codes, ds.attrisize, ds.gamma, ds.v, ds.w)
+    eng.set_seed(1)
+    eng.init_chain(eng.chain_params(m=3, iterations=warm + timed, L=0, burnin=0, neal8=True, split_merge=False,
+                                    t=10, r=10), c_i=ds.truth)
+    eng.iterations(0, warm)
+    eng.drop_prepared()
+    eng.synchronize()
+    acc, ll = eng.iterations(warm, timed)
+    c, cen, sig = eng.get_state()
+    eng.close()
+    assert got["loglik"].shape == (timed,) and np.array_equal(got["loglik"], ll)
+    assert np.array_equal(got["accepted"], acc)
+    assert np.array_equal(got["labels"], c)
+    assert np.array_equal(got["centers"], cen) and np.array_equal(got["sigma"], sig)
