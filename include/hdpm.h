@@ -337,6 +337,35 @@ int hdpm_get_option(hdpm_ctx* ctx, int32_t option, double* value);
 int hdpm_psm_build(hdpm_ctx* ctx, const int32_t* c_trace, int32_t M, int32_t N);
 int hdpm_psm_rows(hdpm_ctx* ctx, int32_t row0, int32_t nrows, double* out);
 int hdpm_psm_vi_lb(hdpm_ctx* ctx, const int32_t* cls, int32_t ncand, double* out);
+/* The same analysis from the saved labels alone, with no N x N matrix (O(M N) work and bytes
+ * per candidate; any N that the labels themselves fit).  With T^m[a][b] = #{j: c_j = a,
+ * z_m(j) = b} the contingency table of a candidate c against draw z_m and n^m_b the draw's
+ * cluster sizes, the device keeps one byte per saved label and computes T^m per block of
+ * candidates.  The trace buffers are separate from the psm ones: a context may hold both.
+ *
+ * hdpm_trace_build: M saved label vectors c_trace[M x N], labels 0..254 (HDPM_E_ARG
+ *   otherwise).  table_budget_bytes bounds the table array of one block of candidates
+ *   (M x Ka x Kz x 4 bytes each, Ka / Kz the largest cluster counts of the candidates / the
+ *   draws; at least one candidate per block); 0 means the default, 256 MiB.  No result
+ *   depends on it.
+ * hdpm_trace_terms: all[i] = sum_m n^m[z_m(i)] = M sum_j psm_ij (N values) and same[c][i] =
+ *   sum_m T^m[c_i][z_m(i)] = M sum_{j: c_j = c_i} psm_ij (ncand x N) of candidates
+ *   cls[ncand x N], exact integers.  Either output may be NULL (all alone runs no table pass).
+ * hdpm_trace_losses: per candidate VI.lb(c, psm) (the value of hdpm_psm_vi_lb, from the
+ *   integer sums), the posterior expected VI (mcclust.ext VI(cls, cls.draw)) =
+ *   (sum_a n_a log2 n_a + (1/M) sum_m (sum_b n^m_b log2 n^m_b - 2 sum_ab T^m log2 T^m)) / N,
+ *   and the integers of Binder's loss sum_{i<j} |1(c_i = c_j) - psm_ij| = A + (P - 2 Q) / M:
+ *   binder_Q[c] = sum_m sum_ab C2(T^m[a][b]) and *binder_P = sum_m sum_b C2(n^m_b) (one
+ *   value), C2(x) = x (x - 1) / 2; A = sum_a C2(n_a) is the caller's.  Any output may be NULL.
+ * hdpm_trace_tables (testing and inspection): T^m of every candidate for draws m0 ..
+ *   m0 + nm - 1, out[ncand x nm x 256 x 256].
+ * Candidate labels are 0..254.  HDPM_E_ARG with a message for labels out of range, for a call
+ * before hdpm_trace_build and for m0 + nm > M. */
+int hdpm_trace_build(hdpm_ctx* ctx, const int32_t* c_trace, int32_t M, int32_t N, int64_t table_budget_bytes);
+int hdpm_trace_terms(hdpm_ctx* ctx, const int32_t* cls, int32_t ncand, uint64_t* all, uint64_t* same);
+int hdpm_trace_losses(hdpm_ctx* ctx, const int32_t* cls, int32_t ncand, double* vi_lb, double* vi,
+                      uint64_t* binder_Q, uint64_t* binder_P);
+int hdpm_trace_tables(hdpm_ctx* ctx, const int32_t* cls, int32_t ncand, int32_t m0, int32_t nm, uint32_t* out);
 /* Testing: one draw on the device from log-weights logw[E] (E <= 256) and the uniform rU --
  * the n8:95-102 categorical draw (two_way = 0; *pick = the 0-based index, or -status) or the
  * sm:204-215 two-way draw (two_way = 1, E = 2) -- with the engine's exp, glibc's algorithm

@@ -28,6 +28,7 @@ EXPORTS = (
     "hdpm_set_debug", "hdpm_synchronize", "hdpm_drop_prepared", "hdpm_init_chain", "hdpm_iteration", "hdpm_iterations", "hdpm_iterations_record", "hdpm_record_take", "hdpm_rng_fill_device",
     "hdpm_get_pool_heads", "hdpm_set_option", "hdpm_get_option", "hdpm_debug_draw", "hdpm_debug_math",
     "hdpm_psm_build", "hdpm_psm_rows", "hdpm_psm_vi_lb",
+    "hdpm_trace_build", "hdpm_trace_terms", "hdpm_trace_losses", "hdpm_trace_tables",
 )
 
 OPT_HIG_LOGSPACE = 1
@@ -148,6 +149,10 @@ def lib():
         "hdpm_psm_build": ([vp, vp, i32, i32], C.c_int),
         "hdpm_psm_rows": ([vp, i32, i32, vp], C.c_int),
         "hdpm_psm_vi_lb": ([vp, vp, i32, vp], C.c_int),
+        "hdpm_trace_build": ([vp, vp, i32, i32, i64], C.c_int),
+        "hdpm_trace_terms": ([vp, vp, i32, vp, vp], C.c_int),
+        "hdpm_trace_losses": ([vp, vp, i32, vp, vp, vp, vp], C.c_int),
+        "hdpm_trace_tables": ([vp, vp, i32, i32, i32, vp], C.c_int),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name)

@@ -75,6 +75,15 @@ hipError_t launch_mt_gen(const MtGenArgs& a, hipStream_t s);
 hipError_t launch_psm(const int32_t* trace, int M, int N, uint8_t* lab, uint32_t* cnt, hipStream_t s);
 hipError_t launch_vi_terms(const uint32_t* cnt, int N, int M, const int32_t* cls, int ncand, double* all, double* same,
                            hipStream_t s);
+hipError_t launch_tr_pack(const int32_t* trace, int nm, int N, int Np, uint8_t* lab, hipStream_t s);
+hipError_t launch_tr_sizes(const uint8_t* lab, int Np, int M, uint32_t* sizes, hipStream_t s);
+hipError_t launch_tr_tables(const uint8_t* lab, const uint8_t* cls, int Np, int M, int ncand, int Ka, int Kz,
+                            uint32_t* tab, hipStream_t s);
+hipError_t launch_tr_gather(const uint8_t* lab, const uint8_t* cls, int N, int Np, int M, int ncand, int Ka, int Kz,
+                            const uint32_t* tab, const uint32_t* sizes, uint64_t* all, uint64_t* same,
+                            hipStream_t s);
+hipError_t launch_tr_reduce(const uint32_t* tab, int ncand, int M, int cells, uint64_t* q1, double* l1, uint64_t* q,
+                            double* l, hipStream_t s);
 hipError_t launch_debug_draw(const double* logw, int E, double rU, int two_way, int ocml, int* out, hipStream_t s);
 hipError_t launch_debug_math(const double* x, int64_t n, int fn, int ocml, double* out, hipStream_t s);
 hipError_t launch_lmatrix(const uint8_t* codes_t, int n, int d, int nq, ParamTables cl, int K, double* L,
@@ -751,6 +760,17 @@ struct Ctx {
   DevBuf<uint32_t> d_psm_cnt;
   DevBuf<double> d_psm_all, d_psm_same;
   int psm_N = 0, psm_M = 0;
+  // matrix-free posterior summary (hdpm_trace_*): label bytes (M x Np), cluster sizes of the
+  // draws (M x 256), and per block of candidates their label bytes, contingency tables
+  // (nc x M x Ka x Kz), per-point sums and per-draw / per-candidate reductions
+  DevBuf<uint8_t> d_tr_lab, d_tr_cls;
+  DevBuf<uint32_t> d_tr_sizes, d_tr_tab;
+  DevBuf<uint64_t> d_tr_all, d_tr_same, d_tr_q1, d_tr_q;
+  DevBuf<double> d_tr_l1, d_tr_l;
+  int tr_N = 0, tr_M = 0, tr_Np = 0, tr_Kz = 0;
+  size_t tr_budget = 0;
+  uint64_t tr_P = 0;     // sum_m sum_b C2(n^m_b)
+  double tr_S = 0.0;     // sum_m sum_b n^m_b log2 n^m_b
 
   Rng rng;
 
@@ -5079,9 +5099,9 @@ using hdpm::HipError;
 using hdpm::ScopedPin;
 using hdpm::DevBuf;
 
-#define GUARD(body)                                                            \
+#define GUARD(...)                                                             \
   try {                                                                        \
-    body                                                                       \
+    __VA_ARGS__                                                                \
   } catch (const hdpm::HipError& he) {                                         \
     ctx->err = std::string("HIP error: ") + hipGetErrorString(he.e) + " at " + he.what; \
     return HDPM_E_DEVICE;                                                      \
@@ -5092,6 +5112,78 @@ using hdpm::DevBuf;
     ctx->err = "unknown exception";                                            \
     return HDPM_E_ARG;                                                         \
   }
+
+// ---- matrix-free posterior summary (trace_summary.hip): shared by the hdpm_trace_* calls
+constexpr size_t kTraceBudget = (size_t)256 << 20;   // default table bytes per block of candidates
+constexpr size_t kTraceMaxBlock = 64;                // candidates per block at most (their N x 8-byte sums)
+constexpr size_t kTraceStageWords = (size_t)16 << 20;   // labels uploaded per block of draws (64 MB)
+
+// the candidates' labels checked (0..254); *Ka = the largest cluster count among them
+static int trace_check(Ctx* ctx, const int32_t* cls, int ncand, int* Ka) {
+  if (ctx->tr_N == 0) { ctx->err = "trace: hdpm_trace_build has not been called"; return HDPM_E_ARG; }
+  if (!cls || ncand <= 0) { ctx->err = "trace: no candidate partitions"; return HDPM_E_ARG; }
+  int mx = 0;
+  for (int64_t q = 0; q < (int64_t)ncand * ctx->tr_N; ++q) {
+    if (cls[q] < 0 || cls[q] > 254) { ctx->err = "trace: candidate labels must be in 0..254"; return HDPM_E_ARG; }
+    mx = std::max(mx, cls[q]);
+  }
+  *Ka = mx + 1;
+  return HDPM_OK;
+}
+
+// The candidates in blocks of at most budget / (M x Ka x Kz x 4) (and kTraceMaxBlock): their
+// tables, then the per-point sums (terms; `all` with the first block if want_all) and the
+// per-candidate reductions (reduce); f(c0, nc) runs with the block's results on the device
+// and the stream drained.  A candidate's results do not depend on the block it falls in.
+template <class F>
+static void trace_blocks(Ctx* ctx, const int32_t* cls, int ncand, int Ka, bool terms, bool want_all, bool reduce, F f) {
+  const int N = ctx->tr_N, Np = ctx->tr_Np, M = ctx->tr_M, Kz = ctx->tr_Kz;
+  if (want_all && !terms && !reduce) {
+    // `all` alone needs the draws' sizes only: no tables, no candidate on the device; the
+    // gather runs its sizes row (candidate count 0) and f sees an empty first block
+    ctx->d_tr_all.ensure((size_t)N);
+    HIPCHK(hdpm::launch_tr_gather(ctx->d_tr_lab.p, nullptr, N, Np, M, 0, Ka, Kz, nullptr, ctx->d_tr_sizes.p,
+                                  ctx->d_tr_all.p, nullptr, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    f(0, 0);
+    return;
+  }
+  const size_t per = (size_t)M * Ka * Kz;
+  size_t cb = std::max<size_t>(1, ctx->tr_budget / (per * 4));
+  cb = std::min(std::min(cb, kTraceMaxBlock), (size_t)ncand);
+  ctx->d_tr_cls.ensure(cb * Np);
+  ctx->d_tr_tab.ensure(cb * per);
+  if (terms) ctx->d_tr_same.ensure(cb * N);
+  if (want_all) ctx->d_tr_all.ensure((size_t)N);
+  if (reduce) {
+    ctx->d_tr_q1.ensure(cb * M);
+    ctx->d_tr_l1.ensure(cb * M);
+    ctx->d_tr_q.ensure(cb);
+    ctx->d_tr_l.ensure(cb);
+  }
+  std::vector<uint8_t> bytes(cb * Np);
+  for (int c0 = 0; c0 < ncand; c0 += (int)cb) {
+    const int nc = std::min((int)cb, ncand - c0);
+    std::memset(bytes.data(), 0xFF, bytes.size());
+    for (int c = 0; c < nc; ++c) {
+      const int32_t* cl = cls + (size_t)(c0 + c) * N;
+      uint8_t* row = bytes.data() + (size_t)c * Np;
+      for (int i = 0; i < N; ++i) row[i] = (uint8_t)cl[i];
+    }
+    HIPCHK(hipMemcpyAsync(ctx->d_tr_cls.p, bytes.data(), (size_t)nc * Np, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemsetAsync(ctx->d_tr_tab.p, 0, (size_t)nc * per * 4, ctx->stream));
+    HIPCHK(hdpm::launch_tr_tables(ctx->d_tr_lab.p, ctx->d_tr_cls.p, Np, M, nc, Ka, Kz, ctx->d_tr_tab.p, ctx->stream));
+    if (terms)
+      HIPCHK(hdpm::launch_tr_gather(ctx->d_tr_lab.p, ctx->d_tr_cls.p, N, Np, M, nc, Ka, Kz, ctx->d_tr_tab.p,
+                                    ctx->d_tr_sizes.p, want_all && c0 == 0 ? ctx->d_tr_all.p : nullptr,
+                                    ctx->d_tr_same.p, ctx->stream));
+    if (reduce)
+      HIPCHK(hdpm::launch_tr_reduce(ctx->d_tr_tab.p, nc, M, Ka * Kz, ctx->d_tr_q1.p, ctx->d_tr_l1.p, ctx->d_tr_q.p,
+                                    ctx->d_tr_l.p, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    f(c0, nc);
+  }
+}
 
 extern "C" {
 
@@ -5537,6 +5629,161 @@ int hdpm_psm_vi_lb(hdpm_ctx* h, const int32_t* cls, int32_t ncand, double* out) 
         f = f + (std::log2((double)sz[cl[i]]) + std::log2(all[i]) - 2 * std::log2(same[(size_t)c * N + i])) / N;
       out[c] = f;
     }
+    return HDPM_OK;
+  })
+}
+int hdpm_trace_build(hdpm_ctx* h, const int32_t* c_trace, int32_t M, int32_t N, int64_t table_budget_bytes) {
+  CTX();
+  if (!c_trace || M <= 0 || N <= 0 || table_budget_bytes < 0) { ctx->err = "trace: bad arguments"; return HDPM_E_ARG; }
+  int mx = 0;
+  for (int64_t q = 0; q < (int64_t)M * N; ++q) {
+    if (c_trace[q] < 0 || c_trace[q] > 254) { ctx->err = "trace: labels must be in 0..254"; return HDPM_E_ARG; }
+    mx = std::max(mx, c_trace[q]);
+  }
+  GUARD({
+    ctx->tr_N = 0;   // no trace until this one is complete
+    const int Np = (int)(((int64_t)N + 15) & ~(int64_t)15);
+    ctx->d_tr_lab.ensure((size_t)M * Np);
+    ctx->d_tr_sizes.ensure((size_t)M * 256);
+    ctx->d_tr_q1.ensure((size_t)M);
+    ctx->d_tr_l1.ensure((size_t)M);
+    ctx->d_tr_q.ensure(1);
+    ctx->d_tr_l.ensure(1);
+    {
+      // the int32 labels go up in blocks of draws through one staging buffer, freed at the end
+      const int mb = (int)std::min<size_t>((size_t)M, std::max<size_t>(1, kTraceStageWords / (size_t)N));
+      DevBuf<int32_t> stage;
+      stage.ensure((size_t)mb * N);
+      for (int m0 = 0; m0 < M; m0 += mb) {
+        const int nm = std::min(mb, M - m0);
+        HIPCHK(hipMemcpyAsync(stage.p, c_trace + (size_t)m0 * N, (size_t)nm * N * 4, hipMemcpyHostToDevice,
+                              ctx->stream));
+        HIPCHK(hdpm::launch_tr_pack(stage.p, nm, N, Np, ctx->d_tr_lab.p + (size_t)m0 * Np, ctx->stream));
+      }
+      HIPCHK(hipStreamSynchronize(ctx->stream));
+    }
+    HIPCHK(hipMemsetAsync(ctx->d_tr_sizes.p, 0, (size_t)M * 256 * 4, ctx->stream));
+    HIPCHK(hdpm::launch_tr_sizes(ctx->d_tr_lab.p, Np, M, ctx->d_tr_sizes.p, ctx->stream));
+    HIPCHK(hdpm::launch_tr_reduce(ctx->d_tr_sizes.p, 1, M, 256, ctx->d_tr_q1.p, ctx->d_tr_l1.p, ctx->d_tr_q.p,
+                                  ctx->d_tr_l.p, ctx->stream));
+    HIPCHK(hipMemcpyAsync(&ctx->tr_P, ctx->d_tr_q.p, 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(&ctx->tr_S, ctx->d_tr_l.p, 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    ctx->tr_M = M;
+    ctx->tr_Np = Np;
+    ctx->tr_Kz = mx + 1;
+    ctx->tr_budget = table_budget_bytes > 0 ? (size_t)table_budget_bytes : kTraceBudget;
+    ctx->tr_N = N;
+    return HDPM_OK;
+  })
+}
+int hdpm_trace_terms(hdpm_ctx* h, const int32_t* cls, int32_t ncand, uint64_t* all, uint64_t* same) {
+  CTX();
+  int Ka = 0;
+  if (int st = trace_check(ctx, cls, ncand, &Ka)) return st;
+  if (!all && !same) return HDPM_OK;
+  GUARD({
+    const size_t N = (size_t)ctx->tr_N;
+    trace_blocks(ctx, cls, ncand, Ka, same != nullptr, all != nullptr, false, [&](int c0, int nc) {
+      if (all && c0 == 0) HIPCHK(hipMemcpyAsync(all, ctx->d_tr_all.p, N * 8, hipMemcpyDeviceToHost, ctx->stream));
+      if (same)
+        HIPCHK(hipMemcpyAsync(same + (size_t)c0 * N, ctx->d_tr_same.p, (size_t)nc * N * 8, hipMemcpyDeviceToHost,
+                              ctx->stream));
+      HIPCHK(hipStreamSynchronize(ctx->stream));
+    });
+    return HDPM_OK;
+  })
+}
+int hdpm_trace_losses(hdpm_ctx* h, const int32_t* cls, int32_t ncand, double* vi_lb, double* vi, uint64_t* binder_Q,
+                      uint64_t* binder_P) {
+  CTX();
+  int Ka = 0;
+  if (int st = trace_check(ctx, cls, ncand, &Ka)) return st;
+  GUARD({
+    const int N = ctx->tr_N;
+    const double dM = (double)ctx->tr_M;
+    if (binder_P) *binder_P = ctx->tr_P;
+    if (!vi_lb && !vi && !binder_Q) return HDPM_OK;
+    std::vector<uint64_t> all, same, q;
+    std::vector<double> lall, term, l, lsz((size_t)Ka);
+    std::vector<int> sz((size_t)Ka);
+    trace_blocks(ctx, cls, ncand, Ka, vi_lb != nullptr, vi_lb != nullptr, vi || binder_Q, [&](int c0, int nc) {
+      if (vi_lb) {
+        if (c0 == 0) {
+          all.resize((size_t)N);
+          HIPCHK(hipMemcpyAsync(all.data(), ctx->d_tr_all.p, (size_t)N * 8, hipMemcpyDeviceToHost, ctx->stream));
+        }
+        same.resize((size_t)nc * N);
+        HIPCHK(hipMemcpyAsync(same.data(), ctx->d_tr_same.p, same.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+      }
+      if (vi || binder_Q) {
+        q.resize((size_t)nc);
+        l.resize((size_t)nc);
+        HIPCHK(hipMemcpyAsync(q.data(), ctx->d_tr_q.p, (size_t)nc * 8, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipMemcpyAsync(l.data(), ctx->d_tr_l.p, (size_t)nc * 8, hipMemcpyDeviceToHost, ctx->stream));
+      }
+      HIPCHK(hipStreamSynchronize(ctx->stream));
+      if (vi_lb && c0 == 0) {
+        // log2 sum_j psm_ij is the same for every candidate
+        lall.resize((size_t)N);
+        term.resize((size_t)N);
+        hdpm::parallel_for(N, [&](int64_t i0, int64_t i1) {
+          for (int64_t i = i0; i < i1; ++i) lall[i] = std::log2((double)all[i] / dM);
+        });
+      }
+      for (int c = 0; c < nc; ++c) {
+        const int32_t* cl = cls + (size_t)(c0 + c) * N;
+        std::fill(sz.begin(), sz.end(), 0);
+        for (int i = 0; i < N; ++i) sz[cl[i]]++;
+        for (int a = 0; a < Ka; ++a) lsz[a] = sz[a] > 0 ? std::log2((double)sz[a]) : 0.0;
+        if (vi_lb) {
+          // the expression of hdpm_psm_vi_lb, with psm sums = integer sums / M
+          // (the terms on the host's threads, their sum in index order as there)
+          const uint64_t* sm = same.data() + (size_t)c * N;
+          hdpm::parallel_for(N, [&](int64_t i0, int64_t i1) {
+            for (int64_t i = i0; i < i1; ++i)
+              term[i] = (lsz[cl[i]] + lall[i] - 2 * std::log2((double)sm[i] / dM)) / N;
+          });
+          double f = 0.0;
+          for (int i = 0; i < N; ++i) f = f + term[i];
+          vi_lb[c0 + c] = f;
+        }
+        if (vi) {
+          // mcclust.ext VI(cls, cls.draw): (sum_a n_a log2 n_a + (S - 2 sum_m sum_ab T log2 T) / M) / N
+          double hc = 0.0;
+          for (int a = 0; a < Ka; ++a) hc = hc + (double)sz[a] * lsz[a];
+          vi[c0 + c] = (hc + (ctx->tr_S - 2 * l[c]) / dM) / N;
+        }
+        if (binder_Q) binder_Q[c0 + c] = q[c];
+      }
+    });
+    return HDPM_OK;
+  })
+}
+int hdpm_trace_tables(hdpm_ctx* h, const int32_t* cls, int32_t ncand, int32_t m0, int32_t nm, uint32_t* out) {
+  CTX();
+  int Ka = 0;
+  if (int st = trace_check(ctx, cls, ncand, &Ka)) return st;
+  if (!out || m0 < 0 || nm <= 0 || (int64_t)m0 + nm > ctx->tr_M) {
+    ctx->err = "trace: draws m0 .. m0 + nm - 1 must lie in 0 .. M - 1";
+    return HDPM_E_ARG;
+  }
+  GUARD({
+    const int M = ctx->tr_M, Kz = ctx->tr_Kz;
+    const size_t cells = (size_t)Ka * Kz;
+    std::memset(out, 0, (size_t)ncand * nm * 65536 * 4);
+    std::vector<uint32_t> t((size_t)nm * cells);
+    trace_blocks(ctx, cls, ncand, Ka, false, false, false, [&](int c0, int nc) {
+      for (int c = 0; c < nc; ++c) {
+        HIPCHK(hipMemcpyAsync(t.data(), ctx->d_tr_tab.p + ((size_t)c * M + m0) * cells, t.size() * 4,
+                              hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+        for (int m = 0; m < nm; ++m)
+          for (int a = 0; a < Ka; ++a)
+            std::memcpy(out + (((size_t)(c0 + c) * nm + m) * 256 + a) * 256, t.data() + ((size_t)m * Ka + a) * Kz,
+                        (size_t)Kz * 4);
+      }
+    });
     return HDPM_OK;
   })
 }

@@ -10,7 +10,10 @@ The reference script summarises every run with CRAN packages:
   * ``ESS`` and ``IAT`` (LaplacesDemon) of (total_cls, loglikelihood).
 
 The N x N matrix is built and queried on the device (csrc/posterior.hip through
-``hdpm_psm_*``): at C4 (N = 70k) it has 4.9e9 entries.  ``arandi``, ``ess`` and ``iat`` are
+``hdpm_psm_*``): at C4 (N = 70k) it has 4.9e9 entries.  ``LabelTrace`` gives the same
+summaries of candidate partitions (VI.lb, the expected VI, Binder's loss) from the saved
+labels alone (csrc/trace_summary.hip through ``hdpm_trace_*``), for sizes where the matrix
+cannot be held (C5: N = 1M would be 4 TB).  ``arandi``, ``ess`` and ``iat`` are
 restated on the host.  None of these packages is installed here (no R), so their parity is
 unpinned; ``arandi`` is checked against scikit-learn's adjusted Rand score.
 """
@@ -72,6 +75,121 @@ class PSM:
         return out
 
 
+def _relabel(rows: np.ndarray, what: str) -> np.ndarray:
+    """Each row relabelled 0..K-1 (int32); ValueError above 255 clusters in a row."""
+    dense = np.empty(rows.shape, np.int32)
+    small = np.issubdtype(rows.dtype, np.integer) and rows.size > 0 and rows.min() >= 0 and rows.max() < (1 << 20)
+    for q in range(rows.shape[0]):
+        if small:
+            # ranks of the labels present, by counting (no sort): what np.unique's inverse is
+            present = np.bincount(rows[q]) > 0
+            k = int(present.sum())
+            if k <= 255:
+                dense[q] = (np.cumsum(present) - 1).astype(np.int32)[rows[q]]
+        else:
+            u, dense[q] = np.unique(rows[q], return_inverse=True)
+            k = u.size
+        if k > 255:
+            raise ValueError(f"{what} {q} has {k} clusters; the device packs at most 255")
+    return dense
+
+
+class LabelTrace:
+    """The posterior summaries of ``PSM`` from the saved labels alone, with no N x N matrix
+    (csrc/trace_summary.hip through ``hdpm_trace_*``): O(M N) work and bytes per candidate
+    partition, so it runs at sizes where the matrix cannot be held (C5: N = 1M).
+
+    ``c_trace`` is the M x N matrix of saved labels (results$c_i, any integers), relabelled
+    0..K_m-1 per iteration as ``PSM`` does; ValueError above 255 clusters in an iteration or
+    in a candidate partition.  The device keeps one byte per saved label and, per block of
+    candidates, their contingency tables against every draw; ``table_budget`` (bytes, None:
+    the library's default) bounds that table array and changes no result.
+
+    With T^m the table of a candidate c against draw z_m and n^m the draw's cluster sizes:
+    ``terms`` gives the integer sums M sum_j psm_ij and M sum_{j: c_j = c_i} psm_ij,
+    ``vi_lb`` mcclust.ext VI.lb(c, psm) (the value ``PSM.vi_lb`` gives), ``vi`` the posterior
+    expected VI (mcclust.ext VI(cls, cls.draw)), and ``binder`` Binder's loss
+    sum_{i<j} |1(c_i = c_j) - psm_ij|.  mcclust's own scaling of Binder's loss is unpinned
+    (the package is absent here); only the argmin matters to ``minbinder``."""
+
+    def __init__(self, c_trace, engine=None, device: int = 0, table_budget: int | None = None):
+        from .sampler import Engine
+        tr = np.asarray(c_trace)
+        if tr.ndim != 2 or tr.size == 0:
+            raise ValueError("c_trace must be M x N")
+        self.M, self.N = tr.shape
+        tr = np.ascontiguousarray(_relabel(tr, "iteration"))
+        self._own = engine is None
+        self.eng = Engine(device) if engine is None else engine
+        self.eng._check(self.eng._L.hdpm_trace_build(self.eng._h, ptr(tr), self.M, self.N,
+                                                     int(table_budget or 0)))
+
+    def close(self):
+        if self._own and self.eng is not None:
+            self.eng.close()
+        self.eng = None
+
+    def _cands(self, cls) -> np.ndarray:
+        c = np.atleast_2d(np.asarray(cls))
+        if c.ndim != 2 or c.shape[1] != self.N:
+            raise ValueError("partitions must have N labels")
+        return np.ascontiguousarray(_relabel(c, "candidate partition"))
+
+    def terms(self, cls):
+        """(all, same): all[i] = sum_m n^m[z_m(i)] (N) and same[c][i] = sum_m
+        T^m[c_i][z_m(i)] (ncand x N), uint64, exact."""
+        c = self._cands(cls)
+        all_ = np.zeros(self.N, np.uint64)
+        same = np.zeros(c.shape, np.uint64)
+        self.eng._check(self.eng._L.hdpm_trace_terms(self.eng._h, ptr(c), c.shape[0], ptr(all_), ptr(same)))
+        return all_, same
+
+    def _losses(self, cls, vi_lb=False, vi=False, binder=False):
+        c = self._cands(cls)
+        k = c.shape[0]
+        lb = np.zeros(k) if vi_lb else None
+        v = np.zeros(k) if vi else None
+        q = np.zeros(k, np.uint64) if binder else None
+        p = np.zeros(1, np.uint64) if binder else None
+        self.eng._check(self.eng._L.hdpm_trace_losses(self.eng._h, ptr(c), k, ptr(lb), ptr(v), ptr(q), ptr(p)))
+        return c, lb, v, q, p
+
+    def vi_lb(self, cls) -> np.ndarray:
+        """mcclust.ext VI.lb(cls, psm) of each row of ``cls``."""
+        return self._losses(cls, vi_lb=True)[1]
+
+    def vi(self, cls) -> np.ndarray:
+        """mcclust.ext VI(cls, cls.draw), the posterior expected variation of information,
+        of each row of ``cls``."""
+        return self._losses(cls, vi=True)[2]
+
+    def binder_terms(self, cls):
+        """The integers of Binder's loss A + (P - 2 Q) / M as Python ints: ([A_c], P, [Q_c])."""
+        c, _, _, q, p = self._losses(cls, binder=True)
+        A = []
+        for r in c:
+            n = np.bincount(r).tolist()
+            A.append(sum(x * (x - 1) // 2 for x in n))
+        return A, int(p[0]), [int(x) for x in q]
+
+    def binder(self, cls) -> np.ndarray:
+        """Binder's loss sum_{i<j} |1(c_i = c_j) - psm_ij| of each row of ``cls``: the three
+        integer sums combined as Python ints, one division."""
+        A, P, Q = self.binder_terms(cls)
+        return np.array([a + (P - 2 * q) / self.M for a, q in zip(A, Q)], np.float64)
+
+    def tables(self, cls, m0: int = 0, nm: int | None = None) -> np.ndarray:
+        """T^m of each row of ``cls`` for draws m0 .. m0 + nm - 1 (ncand x nm x 256 x 256
+        uint32; testing and inspection)."""
+        c = self._cands(cls)
+        nm = self.M - int(m0) if nm is None else int(nm)
+        if m0 < 0 or nm <= 0 or m0 + nm > self.M:
+            raise ValueError("draws m0 .. m0 + nm - 1 must lie in 0 .. M - 1")
+        out = np.zeros((c.shape[0], nm, 256, 256), np.uint32)
+        self.eng._check(self.eng._L.hdpm_trace_tables(self.eng._h, ptr(c), c.shape[0], int(m0), nm, ptr(out)))
+        return out
+
+
 def comp_psm(c_trace, device: int = 0) -> np.ndarray:
     """mcclust::comp.psm: the full N x N matrix (moderate N)."""
     p = PSM(c_trace, device=device)
@@ -81,10 +199,21 @@ def comp_psm(c_trace, device: int = 0) -> np.ndarray:
         p.close()
 
 
-def minvi(psm: PSM, cls_draw=None, method: str = "avg", max_k: int | None = None):
+def minvi(psm, cls_draw=None, method: str = "avg", max_k: int | None = None, loss: str = "VI.lb"):
     """mcclust.ext::minVI for the methods "avg" (cuts of the average-linkage tree of
     1 - psm, k = 1..max_k, default ceiling(N / 8); the tree on the host, needs the full
-    matrix) and "draws" (the saved partitions).  Returns (cl, value) with cl 1-based."""
+    matrix) and "draws" (the saved partitions).  Returns (cl, value) with cl 1-based.
+
+    ``psm`` is a ``PSM`` or, for "draws", a ``LabelTrace`` (no matrix: "avg" raises
+    ValueError).  ``loss`` is "VI.lb" (the lower bound minVI minimises) or "VI" (the
+    posterior expected VI itself, mcclust.ext VI(cls, cls.draw); needs a ``LabelTrace``)."""
+    if loss not in ("VI.lb", "VI"):
+        raise ValueError(f"unknown loss {loss!r}")
+    trace = isinstance(psm, LabelTrace)
+    if loss == "VI" and not trace:
+        raise ValueError("loss 'VI' needs a LabelTrace")
+    if trace and method == "avg":
+        raise ValueError("method 'avg' needs the matrix: use a PSM")
     if method == "draws":
         if cls_draw is None:
             raise ValueError("method 'draws' needs cls_draw")
@@ -100,10 +229,30 @@ def minvi(psm: PSM, cls_draw=None, method: str = "avg", max_k: int | None = None
         cand = cut_tree(Z, n_clusters=list(range(1, kmax + 1))).T
     else:
         raise ValueError(f"unknown method {method!r}")
-    vals = psm.vi_lb(cand)
+    vals = psm.vi(cand) if loss == "VI" else psm.vi_lb(cand)
     best = int(np.argmin(vals))
     cl = np.unique(cand[best], return_inverse=True)[1] + 1
     return cl, float(vals[best])
+
+
+def minbinder(trace: LabelTrace, cls_draw=None, method: str = "draws"):
+    """mcclust::minbinder for the method "draws": the saved partition minimising Binder's
+    loss sum_{i<j} |1(c_i = c_j) - psm_ij|, from a ``LabelTrace``.  Returns (cl, value) with
+    cl 1-based.  The argmin is chosen on exact integers (M A + P - 2 Q); the value is
+    ``LabelTrace.binder``'s.  mcclust is absent here, so its scaling of the reported value
+    is unpinned, as minVI's tie conventions are; the argmin does not depend on it."""
+    if not isinstance(trace, LabelTrace):
+        raise ValueError("minbinder needs a LabelTrace")
+    if method != "draws":
+        raise ValueError(f"unknown method {method!r}: only 'draws' runs without the matrix")
+    if cls_draw is None:
+        raise ValueError("method 'draws' needs cls_draw")
+    cand = np.atleast_2d(np.asarray(cls_draw))
+    A, P, Q = trace.binder_terms(cand)
+    num = [trace.M * a + P - 2 * q for a, q in zip(A, Q)]
+    best = min(range(len(num)), key=num.__getitem__)
+    cl = np.unique(cand[best], return_inverse=True)[1] + 1
+    return cl, float(A[best] + (P - 2 * Q[best]) / trace.M)
 
 
 def arandi(cl1, cl2, adjust: bool = True) -> float:
