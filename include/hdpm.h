@@ -293,6 +293,12 @@ int hdpm_get_pool_heads(hdpm_ctx* ctx, uint64_t* out, int64_t P);
  * the limit to -value without that check, so the device-side gate-off (and the engine's
  * recovery from it: the sweep re-run ungated, same chain) can be exercised. */
 #define HDPM_OPT_PIPE_WAIT_US 3
+/* HDPM_OPT_CAPTURE_DELAY_US (testing, default 0): when hdpm_iterations_record has to read a saved
+ * iteration's labels from device memory (the host mirror is invalid), the host sleeps this many
+ * microseconds (at most 1e6) before it issues that read -- long enough for a sweep that went
+ * ahead on the device to have finished, so a test sees whether the read is ordered before it.
+ * Host-side only; same chain either way. */
+#define HDPM_OPT_CAPTURE_DELAY_US 10
 /* HDPM_OPT_FPG_WAIT_US: the limit, in microseconds, after which a grid barrier of the device-wide
  * resolver (k_resolve_fpg) gives up (default 2 s).  A launch that gives up has committed
  * exactly the windows before the barrier; it ends as a restart there and the engine continues

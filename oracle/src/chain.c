@@ -7,11 +7,13 @@
 #include <stdlib.h>
 #include <string.h>
 
-/* la:6-174 */
-int orc_run_markov_chain(const double* data, int n, int d, const int* attrisize, double gamma,
-                         const double* v, const double* w, const orc_chain_params* p,
-                         const int* c_i_init, int32_t* rng_state, int* out_total_cls, int* out_c_i,
-                         double* out_loglik, int* out_accepted, int* final_ass) {
+/* la:6-174, plus the optional trace outputs (see oracle.h); the trace only reads the state. */
+int orc_run_markov_chain_trace(const double* data, int n, int d, const int* attrisize, double gamma,
+                               const double* v, const double* w, const orc_chain_params* p,
+                               const int* c_i_init, int32_t* rng_state, int* out_total_cls,
+                               int* out_c_i, double* out_loglik, int* out_accepted, int* final_ass,
+                               int* out_moves, int* out_k_all, double* out_centers,
+                               double* out_sigmas, int64_t trace_rows_cap) {
     orc_aux A = {n, d, data, attrisize, gamma, v, w, NULL};
     uint8_t* codes = p->fast >= 2 ? orc_codes_rowmajor(&A) : NULL;   /* optimised oracle */
     A.codes = codes;
@@ -22,6 +24,12 @@ int orc_run_markov_chain(const double* data, int n, int d, const int* attrisize,
     if (st) return st;
     orc_pool pool = {0, d, NULL, NULL};
     int* counts = NULL;
+    int* prev = NULL;            /* labels at the start of the iteration (out_moves only) */
+    int64_t trace_rows = 0;      /* rows of out_centers / out_sigmas written so far */
+    if (out_moves) {
+        prev = (int*)malloc(sizeof(int) * (size_t)n);
+        if (!prev) { st = ORC_E_ARG; goto out; }
+    }
     /* la:30-43 initial assignment */
     s.total_cls = p->L;
     if (c_i_init) {
@@ -55,6 +63,7 @@ int orc_run_markov_chain(const double* data, int n, int d, const int* attrisize,
     const int total = (p->iterations + p->burnin) * p->thinning;
     for (int iter = 0; iter < total; ++iter) {
         int accepted = 0;
+        if (prev) memcpy(prev, s.c_i, sizeof(int) * (size_t)n);
         if (p->neal8 && iter % p->n8_step_size == 0) {   /* la:94-103 */
             if (p->fast) {
                 st = orc_validate_state(&s);
@@ -83,6 +92,12 @@ int orc_run_markov_chain(const double* data, int n, int d, const int* attrisize,
             st = orc_pool_generate(&rng, &A, &pool);
             if (st) goto out;
         }
+        if (out_moves) {
+            int mv = 0;
+            for (int i = 0; i < n; i++) mv += s.c_i[i] != prev[i];
+            out_moves[iter] = mv;
+        }
+        if (out_k_all) out_k_all[iter] = s.total_cls;
         const int rec = iter >= p->thinning * p->burnin && iter % p->thinning == 0;
         double ll = 0.0;
         if (rec || !p->fast)                                    /* la:132 */
@@ -93,12 +108,28 @@ int orc_run_markov_chain(const double* data, int n, int d, const int* attrisize,
             if (out_c_i) memcpy(out_c_i + (size_t)at * n, s.c_i, sizeof(int) * (size_t)n);
             if (out_loglik) out_loglik[at] = ll;
             if (out_accepted) out_accepted[at] = accepted;
+            if (out_centers || out_sigmas) {
+                if (trace_rows + s.total_cls > trace_rows_cap) { st = ORC_E_ARG; goto out; }
+                const size_t off = (size_t)trace_rows * d, len = sizeof(double) * (size_t)s.total_cls * d;
+                if (out_centers) memcpy(out_centers + off, s.center, len);
+                if (out_sigmas) memcpy(out_sigmas + off, s.sigma, len);
+                trace_rows += s.total_cls;
+            }
         }
     }
     if (final_ass) memcpy(final_ass, s.c_i, sizeof(int) * (size_t)n);
 out:
     orc_rng_export(&rng, rng_state);
-    free(pool.center); free(pool.sigma); free(counts); free(codes);
+    free(pool.center); free(pool.sigma); free(counts); free(codes); free(prev);
     orc_state_free(&s);
     return st;
+}
+
+int orc_run_markov_chain(const double* data, int n, int d, const int* attrisize, double gamma,
+                         const double* v, const double* w, const orc_chain_params* p,
+                         const int* c_i_init, int32_t* rng_state, int* out_total_cls, int* out_c_i,
+                         double* out_loglik, int* out_accepted, int* final_ass) {
+    return orc_run_markov_chain_trace(data, n, d, attrisize, gamma, v, w, p, c_i_init, rng_state,
+                                      out_total_cls, out_c_i, out_loglik, out_accepted, final_ass,
+                                      NULL, NULL, NULL, NULL, 0);
 }

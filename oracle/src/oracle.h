@@ -153,6 +153,21 @@ int orc_run_markov_chain(const double* data_colmajor, int n, int d, const int* a
                          int* out_total_cls, int* out_c_i, double* out_loglik, int* out_accepted,
                          int* final_ass);
 
+/* The same chain with optional trace outputs (each may be NULL; all NULL is exactly
+ * orc_run_markov_chain, which is a thin call of this function):
+ *   out_moves[iter], out_k_all[iter]  for every one of the (iterations+burnin)*thinning
+ *     iterations: the number of points whose label differs between the start and the end of
+ *     that iteration, and total_cls after it;
+ *   out_centers, out_sigmas  per saved iteration its total_cls x d centers / sigmas, appended
+ *     row-wise (saved iteration `at` starts at row sum(out_total_cls[0..at-1])).
+ *     trace_rows_cap is the capacity of each in rows of d doubles; ORC_E_ARG if it is exceeded. */
+int orc_run_markov_chain_trace(const double* data_colmajor, int n, int d, const int* attrisize,
+                               double gamma, const double* v, const double* w,
+                               const orc_chain_params* p, const int* c_i_init, int32_t* rng_state,
+                               int* out_total_cls, int* out_c_i, double* out_loglik,
+                               int* out_accepted, int* final_ass, int* out_moves, int* out_k_all,
+                               double* out_centers, double* out_sigmas, int64_t trace_rows_cap);
+
 #ifdef __cplusplus
 }
 #endif

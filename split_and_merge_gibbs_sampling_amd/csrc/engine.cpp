@@ -1619,11 +1619,20 @@ struct Ctx {
   }
   // The labels on the host before the device can change them again (the recording path, right
   // after a sweep): the mirror, the move log applied to it, or a download (on cstream: the
-  // sweep stream may hold a sweep enqueued ahead behind its wait kernel).
+  // sweep stream may hold a sweep enqueued ahead behind its wait kernel).  Nothing on the device
+  // orders the copy before that sweep: the host does, by giving its go (pipe_go) only after this
+  // call.  A sweep whose wait kernel could give the go itself (PipeAuto) would start as soon as
+  // this sweep's control block shows no move, beside the copy, and its resolver and k_relabel
+  // write d_c; pre_enqueue therefore leaves the device go off behind a recorded sweep that
+  // reads the labels from the device (record_now).
+  bool record_now = false;             // iteration(): this sweep's labels are recorded
+  double capture_delay_us = 0.0;       // HDPM_OPT_CAPTURE_DELAY_US (testing)
   void capture_labels() {
     if (host_c_valid) return;
-    // behind the last sweep end (slot ids -> labels, the move log complete); a sweep enqueued
-    // ahead sits behind it on `stream`, so the wait cannot reach that sweep's gate
+    if (capture_delay_us > 0.0) std::this_thread::sleep_for(std::chrono::duration<double, std::micro>(capture_delay_us));
+    // behind the last sweep end (slot ids -> labels, the move log complete).  ev_labels is the
+    // end of the last sweep that moved points, possibly many sweeps back: it does not order the
+    // copy against anything enqueued after it.
     if (ev_labels) HIPCHK(hipStreamWaitEvent(cstream, ev_labels, 0));
     if (mirror_moves > 0) {
       mlog_h.resize((size_t)3 * mirror_moves);
@@ -2631,7 +2640,11 @@ struct Ctx {
       return e && e[0] == '0';
     }();
     PipeAuto au{};
-    if (dev && pipe_auto && !auto_env_off && dspec.ran && dspec.fast && dspec.chain && whole >= 0) {
+    // (not behind a recorded sweep whose labels capture_labels will read from the device: the
+    // mirror is invalid now and a sweep leaves it so; the host's go comes after that copy)
+    const bool labels_from_device = record_now && !host_c_valid;
+    if (dev && pipe_auto && !auto_env_off && dspec.ran && dspec.fast && dspec.chain && whole >= 0 &&
+        !labels_from_device) {
       const RngWindow& w = win[whole];
       au = PipeAuto{dspec.chain, w.raw.p, (int64_t)w.start_pos, w.count, (int64_t)n * (m + 1), 1};
     }
@@ -4976,13 +4989,16 @@ int Ctx::iteration(const hdpm_chain_params* p, int iter, int* idx_1_sm, int* acc
   if (n8) {                                              // la:94-103
     // the next sweep may be enqueued while this one's update is drawn (pre_enqueue)
     deep_ok = early && launch_next && !(debug & 4194304);
+    record_now = labels_out != nullptr;
     st = neal8_sweep(p->m);
     deep_ok = false;
+    record_now = false;
     if (st) {
       pre_release();
       return st;
     }
-    // a recorded iteration's labels, before a sweep enqueued ahead can be given the go
+    // a recorded iteration's labels, before the host gives a sweep enqueued ahead its go (the
+    // device go is not armed behind a recorded sweep that downloads them, see capture_labels)
     if (labels_out) capture_labels();
     defer_commit = early;
     st = update_phi(nullptr, 0);
@@ -5502,6 +5518,7 @@ int hdpm_get_option(hdpm_ctx* h, int32_t option, double* value) {
     case HDPM_OPT_LAT_NEGLIGIBLE: *value = ctx->lat_negl; return HDPM_OK;
     case HDPM_OPT_SM_WIDE_WAIT_US: *value = (double)ctx->sm_wide_ticks * 0.01; return HDPM_OK;
     case HDPM_OPT_SM_CHAIN: *value = (double)ctx->sm_chain_mode; return HDPM_OK;
+    case HDPM_OPT_CAPTURE_DELAY_US: *value = ctx->capture_delay_us; return HDPM_OK;
     default:
       ctx->err = "unknown option";
       return HDPM_E_ARG;
@@ -5559,6 +5576,10 @@ int hdpm_set_option(hdpm_ctx* h, int32_t option, double value) {
       GUARD(ctx->cancel_ahead();)
       ctx->pipe_limit_ticks = std::max(1LL, (long long)(std::fabs(value) * 100.0));
       ctx->pipe_host_check = value > 0;
+      return HDPM_OK;
+    case HDPM_OPT_CAPTURE_DELAY_US:
+      if (!(value >= 0.0) || !(value <= 1e6)) { ctx->err = "capture delay must be in [0, 1e6] us"; return HDPM_E_ARG; }
+      ctx->capture_delay_us = value;
       return HDPM_OK;
     default:
       ctx->err = "unknown option";

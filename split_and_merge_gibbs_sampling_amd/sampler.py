@@ -227,6 +227,11 @@ class Engine:
         ahead; negative: no host-side check (exercises the device gate-off recovery)."""
         self._check(self._L.hdpm_set_option(self._h, _lib.OPT_PIPE_WAIT_US, float(us)))
 
+    def set_capture_delay_us(self, us: float):
+        """Testing (include/hdpm.h HDPM_OPT_CAPTURE_DELAY_US): the host's sleep before
+        iterations_record reads a saved iteration's labels from device memory (0: none)."""
+        self._check(self._L.hdpm_set_option(self._h, _lib.OPT_CAPTURE_DELAY_US, float(us)))
+
     def set_fpg_wait_us(self, us: float):
         """The grid-barrier limit of the device-wide resolver (include/hdpm.h
         HDPM_OPT_FPG_WAIT_US); a launch that gives up is continued on one workgroup."""

@@ -10,9 +10,9 @@
 //   the NumericMatrix); uint32 seed (set.seed); int32 ncalls; per call: int32 params[12]
 //   (hdpm_chain_params order), int32 has_init, int32 init[n] when has_init.
 // Output: one line per poisoned input and per call; exit status 0 when every check passes.
-// Compared per call: the status, and on success total_cls, c_i, accepted and final_ass
-// bit for bit, log-likelihoods within 1e-10 relative (north_star), the 625-word stream
-// after the call.  On an error status both sides must stop with the same status.
+// Compared per call: the status, and on success total_cls, c_i, accepted, final_ass and every
+// saved iteration's centers and sigmas (the oracle's traced driver) bit for bit,
+// log-likelihoods within 1e-10 relative (north_star), the 625-word stream after the call.  On an error status both sides must stop with the same status.
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -28,10 +28,11 @@ typedef struct {
   int neal8, split_merge, n8_step_size, sam_step_size, thinning;
   int fast;
 } orc_chain_params;
-int orc_run_markov_chain(const double* data_colmajor, int n, int d, const int* attrisize, double gamma,
-                         const double* v, const double* w, const orc_chain_params* p, const int* c_i_init,
-                         int32_t* rng_state, int* out_total_cls, int* out_c_i, double* out_loglik, int* out_accepted,
-                         int* final_ass);
+int orc_run_markov_chain_trace(const double* data_colmajor, int n, int d, const int* attrisize, double gamma,
+                               const double* v, const double* w, const orc_chain_params* p, const int* c_i_init,
+                               int32_t* rng_state, int* out_total_cls, int* out_c_i, double* out_loglik,
+                               int* out_accepted, int* final_ass, int* out_moves, int* out_k_all,
+                               double* out_centers, double* out_sigmas, int64_t trace_rows_cap);
 void orc_ffi_set_seed(uint32_t seed, int32_t* state);
 }
 
@@ -96,9 +97,13 @@ int main(int argc, char** argv) {
     const int it = p.iterations;
     std::vector<int> tot(it), cis((size_t)it * n), acc(it), fin(n);
     std::vector<double> ll(it);
-    const int so = orc_run_markov_chain(data.data(), n, d, att.data(), gamma, v.data(), w.data(), &op,
-                                        has_init ? init.data() : nullptr, st_orc.data(), tot.data(), cis.data(),
-                                        ll.data(), acc.data(), fin.data());
+    // every saved iteration's K x d centers and sigmas, appended row-wise (K <= n + 2)
+    const int64_t cap = (int64_t)it * (n + 2);
+    std::vector<double> ocen((size_t)cap * d), osig((size_t)cap * d);
+    const int so = orc_run_markov_chain_trace(data.data(), n, d, att.data(), gamma, v.data(), w.data(), &op,
+                                              has_init ? init.data() : nullptr, st_orc.data(), tot.data(),
+                                              cis.data(), ll.data(), acc.data(), fin.data(), nullptr, nullptr,
+                                              ocen.data(), osig.data(), cap);
     hdpm_adapter::ChainResult res;
     std::string err;
     const auto wall0 = std::chrono::steady_clock::now();
@@ -109,7 +114,8 @@ int main(int argc, char** argv) {
     if (so != se) {
       why = "status oracle " + std::to_string(so) + " engine " + std::to_string(se) + " (" + err + ")";
     } else if (so == 0) {
-      for (int a = 0; a < it && why.empty(); ++a) {
+      size_t row = 0;                    // of saved iteration a in ocen / osig
+      for (int a = 0; a < it && why.empty(); row += (size_t)tot[a], ++a) {
         if (res.total_cls[a] != tot[a]) why = "total_cls at " + std::to_string(a);
         else if (std::memcmp(res.c_i[a].data(), &cis[(size_t)a * n], (size_t)n * 4) != 0) why = "c_i at " + std::to_string(a);
         else if (res.accepted[a] != acc[a]) why = "accepted at " + std::to_string(a);
@@ -117,6 +123,10 @@ int main(int argc, char** argv) {
           why = "loglikelihood at " + std::to_string(a);
         else if (res.centers[a].size() != (size_t)tot[a] * d || res.sigmas[a].size() != (size_t)tot[a] * d)
           why = "centers / sigmas shape at " + std::to_string(a);
+        else if (std::memcmp(res.centers[a].data(), &ocen[row * d], (size_t)tot[a] * d * 8) != 0)
+          why = "centers at " + std::to_string(a);
+        else if (std::memcmp(res.sigmas[a].data(), &osig[row * d], (size_t)tot[a] * d * 8) != 0)
+          why = "sigmas at " + std::to_string(a);
       }
       if (why.empty() && std::memcmp(res.final_ass.data(), fin.data(), (size_t)n * 4) != 0) why = "final_ass";
       if (why.empty() && st_eng != st_orc) why = "random stream after the call";

@@ -80,6 +80,8 @@ def lib():
         L.orc_run_markov_chain.argtypes = [_f64p, C.c_int, C.c_int, _i32p, C.c_double, _f64p, _f64p,
                                            C.POINTER(ChainParams), C.c_void_p, _i32p, _i32p, _i32p,
                                            _f64p, _i32p, _i32p]
+        L.orc_run_markov_chain_trace.argtypes = L.orc_run_markov_chain.argtypes + [
+            _i32p, _i32p, _f64p, _f64p, C.c_int64]
         _lib = L
     return _lib
 
@@ -279,8 +281,14 @@ def split_and_merge(codes, attrisize, gamma, v, w, state: OracleState, t, r, idx
 
 def run_markov_chain(codes, attrisize, gamma, v, w, *, m=5, iterations=1000, L=1, c_i=None,
                      burnin=5000, t=10, r=10, neal8=False, split_merge=True, n8_step_size=1,
-                     sam_step_size=1, thinning=1, rng=None, seed=None, fast=1):
-    """Oracle restatement of run_markov_chain (la:6-174).  Returns (status, results dict)."""
+                     sam_step_size=1, thinning=1, rng=None, seed=None, fast=1, trace=False, trace_rows=None):
+    """Oracle restatement of run_markov_chain (la:6-174).  Returns (status, results dict).
+
+    trace=True (orc_run_markov_chain_trace) adds, for every one of the (iterations+burnin)*thinning
+    iterations, `moves` (points whose label changed during it) and `k_all` (K after it), and for
+    every saved iteration its K x d `centers` and `sigmas` (lists of arrays, the layout of
+    Engine.iterations_record).  trace_rows: capacity for the saved rows (default: the n + 2 labels
+    a state can hold, per saved iteration; untouched pages of it are never committed)."""
     codes = np.asarray(codes)
     n, d = codes.shape
     if rng is None:
@@ -297,8 +305,22 @@ def run_markov_chain(codes, attrisize, gamma, v, w, *, m=5, iterations=1000, L=1
         cptr = ci.ctypes.data
     else:
         ci, cptr = None, None
-    st = lib().orc_run_markov_chain(colmajor(codes), n, d, np.ascontiguousarray(attrisize, np.int32),
-                                    gamma, np.ascontiguousarray(v, np.float64),
-                                    np.ascontiguousarray(w, np.float64), C.byref(p), cptr, rng, tot,
-                                    cis.reshape(-1), ll, acc, fin)
-    return st, {"total_cls": tot, "c_i": cis, "loglikelihood": ll, "accepted": acc, "final_ass": fin}
+    args = (colmajor(codes), n, d, np.ascontiguousarray(attrisize, np.int32), gamma,
+            np.ascontiguousarray(v, np.float64), np.ascontiguousarray(w, np.float64), C.byref(p), cptr, rng,
+            tot, cis.reshape(-1), ll, acc, fin)
+    res = {"total_cls": tot, "c_i": cis, "loglikelihood": ll, "accepted": acc, "final_ass": fin}
+    if not trace:
+        return lib().orc_run_markov_chain(*args), res
+    total = (iterations + burnin) * thinning
+    moves = np.zeros(total, np.int32)
+    k_all = np.zeros(total, np.int32)
+    cap = int(trace_rows) if trace_rows is not None else iterations * (n + 2)
+    cen = np.empty((max(cap, 1), d), np.float64)
+    sig = np.empty((max(cap, 1), d), np.float64)
+    st = lib().orc_run_markov_chain_trace(*args, moves, k_all, cen.reshape(-1), sig.reshape(-1), cap)
+    if st == 0:
+        off = np.concatenate([[0], np.cumsum(tot, dtype=np.int64)])
+        res["centers"] = [cen[off[q]:off[q + 1]].copy() for q in range(iterations)]
+        res["sigmas"] = [sig[off[q]:off[q + 1]].copy() for q in range(iterations)]
+    res["moves"], res["k_all"] = moves, k_all
+    return st, res

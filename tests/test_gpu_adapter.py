@@ -5,8 +5,9 @@ integration/launcher_hip.cpp is the reference's R entry point run_markov_chain
 R types, and tests/cpp/adapter_replay.cpp (built by __graft_entry__.build into
 integration/adapter_replay) runs it against the oracle's run_markov_chain (la:6-174) over
 consecutive calls sharing one random stream: .Random.seed in (hdpm_rng_set_state) ->
-hdpm_init_chain -> hdpm_iteration loop with hdpm_get_state at every saved iteration ->
-hdpm_rng_get_state -> the next call.  Labels, K, acceptances, final_ass and the stream
+hdpm_init_chain -> hdpm_iterations_record in batches of 64 with hdpm_record_take after each ->
+hdpm_get_state (final_ass) -> hdpm_rng_get_state -> the next call.  Labels, K, acceptances,
+every saved iteration's centers and sigmas (the oracle's traced driver), final_ass and the stream
 after each call bit for bit, log-likelihoods within 1e-10 relative; `time` inside the call's
 wall time (the clock starts after init_chain, la:79); non-integer or out-of-range doubles in
 the data matrix rejected with HDPM_E_ARG before any narrowing cast.

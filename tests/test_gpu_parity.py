@@ -417,46 +417,161 @@ def test_run_markov_chain_keep_params_and_stream_handback(hd, oracle, zoo):
     assert ost == 0 and np.array_equal(ref2["c_i"], c["c_i"]) and np.array_equal(c["rng_state"], st)
 
 
-@pytest.mark.parametrize("shape", ["settled", "moving"])
-def test_iterations_record_matches_stepwise(hd, oracle, shape):
-    """hdpm_iterations_record (the adapter's sampling loop, la:139-153, thinning 1 and 2): every
-    saved iteration's K, labels, centers and sigmas equal what hdpm_iteration + hdpm_get_state
-    give step by step, the labels equal the oracle's chain; the labels come from the host mirror
-    (the sweep's move log applied) rather than N-word downloads once the chain settles."""
-    ds = synth(20000, 64, 8, 4, seed=71) if shape == "settled" else synth(6000, 32, 6, 2, seed=72)
-    for thinning in (1, 2):
-        iters, burnin = 12, 2
-        kw = dict(m=3, iterations=iters, L=1, c_i=ds.truth, burnin=burnin, neal8=True, split_merge=False,
-                  thinning=thinning)
-        st, ref = oracle.run_markov_chain(ds.codes, ds.attrisize, ds.gamma, ds.v, ds.w, seed=8, fast=1, **kw)
+_record_refs = {}
+
+
+def record_reference(oracle, shape, thinning):
+    """The record tests' data set and the oracle's traced chain on it, computed once per
+    (shape, thinning) and shared by the phi cases (read-only).  The settled shape's 20000 x 64
+    chain runs on the optimised oracle (fast=2: the same draws and arithmetic, pinned bit for bit
+    to fast=1 by tests/test_oracle.py), which keeps a case within a few seconds."""
+    key = (shape, thinning)
+    if key not in _record_refs:
+        ds = synth(20000, 64, 8, 4, seed=71) if shape == "settled" else synth(6000, 32, 6, 2, seed=72)
+        kw = dict(m=3, iterations=12, L=1, c_i=ds.truth, burnin=2, neal8=True, split_merge=False, thinning=thinning)
+        st, ref = oracle.run_markov_chain(ds.codes, ds.attrisize, ds.gamma, ds.v, ds.w, seed=8,
+                                          fast=2 if shape == "settled" else 1, trace=True, **kw)
         assert st == 0
-        a = make_engine(hd, ds)
-        a.set_seed(8)
-        p = a.chain_params(m=3, iterations=iters, L=1, burnin=burnin, neal8=True, split_merge=False, thinning=thinning)
-        a.init_chain(p, c_i=ds.truth)
-        total = (iters + burnin) * thinning
-        acc, ll, kk, cis, cens, sigs = a.iterations_record(0, 5)
-        acc2, ll2, kk2, cis2, cens2, sigs2 = a.iterations_record(5, total - 5)
-        kk, cis = np.concatenate([kk, kk2]), np.concatenate([cis, cis2])
-        cens, sigs, ll = cens + cens2, sigs + sigs2, np.concatenate([ll, ll2])
-        stats = a.stats()
-        a.close()
-        assert len(kk) == iters and np.array_equal(cis, ref["c_i"]) and np.array_equal(kk, ref["total_cls"])
-        b = make_engine(hd, ds)
-        b.set_seed(8)
-        b.init_chain(p, c_i=ds.truth)
-        q = 0
-        for it in range(total):
-            _, lik = b.iteration(it)
-            assert lik == ll[it]
-            if it >= thinning * burnin and it % thinning == 0:
-                c, cen, sig = b.get_state()
-                assert np.array_equal(c, cis[q]) and np.array_equal(cen, cens[q]) and np.array_equal(sig, sigs[q])
-                q += 1
-        b.close()
-        assert q == iters
+        for v in ref.values():
+            for x in (v if isinstance(v, list) else [v]):
+                x.setflags(write=False)
+        _record_refs[key] = (ds, ref)
+    return _record_refs[key]
+
+
+@pytest.mark.parametrize("phi", ["host", "device"])
+@pytest.mark.parametrize("thinning", [1, 2, 3])
+@pytest.mark.parametrize("shape", ["settled", "moving"])
+def test_iterations_record_matches_stepwise(hd, oracle, shape, thinning, phi):
+    """hdpm_iterations_record (the adapter's sampling loop, la:139-153, thinning 1 to 3): every
+    saved iteration's K, labels, centers and sigmas equal what hdpm_iteration + hdpm_get_state
+    give step by step, and the oracle's traced chain: labels, K, centers and sigmas bit for bit,
+    the log-likelihood within RTOL.  update_phi on the host or forced onto the device (K * d is
+    below the automatic placement's 4096 items here): the speculative device update, its chained
+    updates and, on the settled shape, the sweeps the device starts itself (pipe_auto).  The labels
+    come from the host mirror (the sweep's move log applied) rather than N-word downloads once
+    the chain settles."""
+    ds, ref = record_reference(oracle, shape, thinning)
+    iters, burnin = 12, 2
+    a = make_engine(hd, ds)
+    a.set_phi_device(phi == "device")
+    a.set_seed(8)
+    p = a.chain_params(m=3, iterations=iters, L=1, burnin=burnin, neal8=True, split_merge=False, thinning=thinning)
+    a.init_chain(p, c_i=ds.truth)
+    total = (iters + burnin) * thinning
+    acc, ll, kk, cis, cens, sigs = a.iterations_record(0, 5)
+    acc2, ll2, kk2, cis2, cens2, sigs2 = a.iterations_record(5, total - 5)
+    kk, cis = np.concatenate([kk, kk2]), np.concatenate([cis, cis2])
+    cens, sigs, ll = cens + cens2, sigs + sigs2, np.concatenate([ll, ll2])
+    stats = a.stats()
+    a.close()
+    print(shape, thinning, phi, {k: stats[k] for k in ("phi_device_calls", "phi_fast_calls", "pipe_auto", "pipe_enqueued",
+                                                      "labels_downloaded", "labels_mirrored", "pipe_desync")})
+    assert len(kk) == iters and np.array_equal(cis, ref["c_i"]) and np.array_equal(kk, ref["total_cls"])
+    assert len(cens) == len(sigs) == iters
+    for q in range(iters):
+        assert np.array_equal(cens[q], ref["centers"][q]), q
+        assert np.array_equal(sigs[q], ref["sigmas"][q]), q
+    saved = [it for it in range(total) if it >= thinning * burnin and it % thinning == 0]
+    np.testing.assert_allclose(ll[saved], ref["loglikelihood"], rtol=RTOL, atol=0)
+    b = make_engine(hd, ds)
+    b.set_phi_device(phi == "device")
+    b.set_seed(8)
+    b.init_chain(p, c_i=ds.truth)
+    q = 0
+    for it in range(total):
+        _, lik = b.iteration(it)
+        assert lik == ll[it]
+        if it >= thinning * burnin and it % thinning == 0:
+            c, cen, sig = b.get_state()
+            assert np.array_equal(c, cis[q]) and np.array_equal(cen, cens[q]) and np.array_equal(sig, sigs[q])
+            q += 1
+    b.close()
+    assert q == iters
+    assert stats["pipe_desync"] == 0, stats
+    if shape == "settled":
+        assert stats["labels_downloaded"] <= 2, stats
+    if phi == "device":
+        assert stats["phi_device_calls"] > 0, stats
         if shape == "settled":
-            assert stats["labels_downloaded"] <= 2, stats
+            assert stats["pipe_auto"] > 0, stats
+
+
+def record_hits(ref, thinning, burnin, total):
+    """Recorded iterations N at which a sweep started by the device could overtake the label
+    download: sweeps N - 1 and N moved nothing (sweep N + 1 is enqueued ahead inside sweep N and
+    its wait kernel finds no move), sweep N + 1 moves points (its labels differ), K constant
+    over the three, and an unrecorded sweep after the previous recorded iteration and before
+    N - 1 moved points (the host mirror is invalid at N, so the labels are downloaded)."""
+    mv, k = ref["moves"], ref["k_all"]
+    rec = [it for it in range(total) if it >= thinning * burnin and it % thinning == 0]
+    hits = []
+    for i, N in enumerate(rec):
+        prev = rec[i - 1] if i else -1
+        if N < 1 or N + 1 >= total:
+            continue
+        if (mv[N] == 0 and mv[N - 1] == 0 and mv[N + 1] > 0 and k[N - 1] == k[N] == k[N + 1]
+                and mv[prev + 1:N - 1].sum() > 0):
+            hits.append(N)
+    return hits
+
+
+# The capture delay of the test below.  On an MI355X the parent commit's iterations_record on
+# these inputs takes 123 - 133 us per iteration (wall time of the second call / its 25 - 26
+# iterations, three runs each; the first call's 0.74 s holds the context's one-off setup and says
+# nothing about a sweep).  20 ms is 150 times that: a sweep that went ahead has finished --
+# resolver, k_relabel and all -- long before the host issues the copy.  (With the parent's
+# ordering and this delay the recorded labels at every hit were the next iteration's.)
+CAPTURE_ITER_US = 133.0
+CAPTURE_DELAY_US = 20000.0
+
+
+@pytest.mark.parametrize("thinning,iters,seed", [(4, 12, 23), (3, 16, 21)])
+def test_record_labels_not_overtaken_by_device_go(hd, oracle, thinning, iters, seed):
+    """A recorded iteration's labels are the labels after its own sweep, also where the sweep
+    enqueued ahead could be started by the device itself (k_pipe_wait's own go, PipeAuto) while
+    the host still has to download them: quiet sweeps N - 1 and N, the mirror invalidated by an
+    earlier unrecorded sweep, sweep N + 1 moving points (record_hits, from the oracle's traced
+    move counts).  HDPM_OPT_CAPTURE_DELAY_US holds the host back before the download, long
+    enough for such a sweep to finish; every recorded row must still equal the oracle's, with
+    the delay and without."""
+    ds = synth(3000, 32, 6, 3, seed=1)
+    burnin = 1
+    kw = dict(m=3, iterations=iters, L=1, c_i=ds.truth, burnin=burnin, neal8=True, split_merge=False,
+              thinning=thinning)
+    st, ref = oracle.run_markov_chain(ds.codes, ds.attrisize, ds.gamma, ds.v, ds.w, seed=seed, fast=1, trace=True, **kw)
+    assert st == 0
+    total = (iters + burnin) * thinning
+    hits = record_hits(ref, thinning, burnin, total)
+    print("hits", hits, "moves", ref["moves"].tolist())
+    assert len(hits) >= 2, hits          # a condition of the test: the chain reaches the path
+    # the last iteration of a call launches no next sweep: the calls split away from every hit
+    split = next(s for s in range(total // 2, total - 1) if all(s - N not in (0, 1, 2) for N in hits))
+    assert min(hits) < split - 2 and split < total
+    assert CAPTURE_DELAY_US >= 100 * CAPTURE_ITER_US
+    for delay in (CAPTURE_DELAY_US, 0.0):
+        eng = make_engine(hd, ds)
+        eng.set_phi_device(True)
+        eng.set_capture_delay_us(delay)
+        eng.set_seed(seed)
+        p = eng.chain_params(m=3, iterations=iters, L=1, burnin=burnin, neal8=True, split_merge=False,
+                             thinning=thinning)
+        eng.init_chain(p, c_i=ds.truth)
+        _, _, kk, cis, cens, sigs = eng.iterations_record(0, split)
+        _, _, kk2, cis2, cens2, sigs2 = eng.iterations_record(split, total - split)
+        kk, cis, cens, sigs = np.concatenate([kk, kk2]), np.concatenate([cis, cis2]), cens + cens2, sigs + sigs2
+        stats = eng.stats()
+        eng.close()
+        print("delay", delay, {k: stats[k] for k in ("pipe_auto", "pipe_enqueued", "labels_downloaded",
+                                                     "labels_mirrored", "pipe_desync", "phi_device_calls")})
+        assert len(kk) == len(cens) == len(sigs) == iters
+        wrong = [q for q in range(iters) if not np.array_equal(cis[q], ref["c_i"][q])]
+        assert not wrong, (delay, "wrong labels at iterations", [(q + burnin) * thinning for q in wrong], "hits", hits)
+        assert np.array_equal(kk, ref["total_cls"]), delay
+        for q in range(iters):
+            assert np.array_equal(cens[q], ref["centers"][q]), (delay, q)
+            assert np.array_equal(sigs[q], ref["sigmas"][q]), (delay, q)
+        assert stats["pipe_auto"] > 0 and stats["labels_downloaded"] > 0 and stats["pipe_desync"] == 0, stats
 
 
 def test_run_markov_chain_random_init_matches_oracle(hd, oracle, zoo):

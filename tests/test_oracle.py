@@ -164,6 +164,54 @@ def test_zoo_split_merge_faithful_equals_fast_and_golden(oracle, zoo):
     assert g["accepted"].sum() > 0
 
 
+@pytest.mark.parametrize("which", ["zoo_sm", "synth_thin3", "synth_fast2"])
+def test_traced_chain_equals_untraced_and_is_consistent(oracle, zoo, which):
+    """orc_run_markov_chain_trace: the trace only reads the state (every untraced result and the
+    random stream position keep their bits); moves / k_all cover every iteration, the saved
+    centers / sigmas are the state the saved labels and log-likelihood belong to."""
+    from split_and_merge_gibbs_sampling_amd.data import hamming_mixture
+    if which == "zoo_sm":
+        ds, c0 = zoo, np.zeros(zoo.n, np.int32)
+        kw = dict(m=3, iterations=20, L=1, c_i=c0, burnin=0, t=5, r=5, neal8=True, split_merge=True, fast=1)
+    else:
+        ds = hamming_mixture(1500, 16, 5, 3, seed=3)
+        c0 = ds.truth
+        kw = dict(m=3, iterations=8, L=1, c_i=c0, burnin=2, neal8=True, split_merge=False, thinning=3,
+                  fast=1 if which == "synth_thin3" else 2)
+    args = (ds.codes, ds.attrisize, ds.gamma, ds.v, ds.w)
+    s0, s1 = oracle.seed_state(5), oracle.seed_state(5)
+    st, ref = oracle.run_markov_chain(*args, rng=s0, **kw)
+    assert st == 0
+    st, res = oracle.run_markov_chain(*args, rng=s1, trace=True, **kw)
+    assert st == 0
+    for k in ("c_i", "total_cls", "loglikelihood", "accepted", "final_ass"):
+        assert np.array_equal(res[k], ref[k]), k
+    assert np.array_equal(s0, s1)
+    iters, burnin, thin = kw["iterations"], kw["burnin"], kw.get("thinning", 1)
+    total = (iters + burnin) * thin
+    assert res["moves"].shape == res["k_all"].shape == (total,)
+    assert np.all(res["moves"] >= 0) and np.all(res["moves"] <= ds.n)
+    saved = [it for it in range(total) if it >= thin * burnin and it % thin == 0]
+    assert np.array_equal(res["k_all"][saved], ref["total_cls"])
+    assert len(res["centers"]) == len(res["sigmas"]) == iters
+    for q in range(iters):
+        K = int(ref["total_cls"][q])
+        assert res["centers"][q].shape == res["sigmas"][q].shape == (K, ds.d)
+        # the traced parameters with the saved labels reproduce the saved log-likelihood
+        state = oracle.OracleState(ref["c_i"][q], K, res["centers"][q], res["sigmas"][q])
+        assert oracle.compute_loglikelihood(ds.codes, ds.attrisize, state, fast=kw["fast"]) == ref["loglikelihood"][q]
+    assert res["centers"][-1].shape == (ref["total_cls"][-1], ds.d)
+    if thin == 1:
+        prev = np.concatenate([(c0 - c0.min())[None], ref["c_i"][:-1]])
+        assert np.array_equal(res["moves"], (ref["c_i"] != prev).sum(axis=1))
+        assert res["moves"].sum() > 0
+    # a capacity one row short of what the saved iterations need is an error, not an overrun
+    st, _ = oracle.run_markov_chain(*args, seed=5, trace=True, trace_rows=int(ref["total_cls"].sum()) - 1, **kw)
+    assert st == 5
+    st, res2 = oracle.run_markov_chain(*args, seed=5, trace=True, trace_rows=int(ref["total_cls"].sum()), **kw)
+    assert st == 0 and all(np.array_equal(a, b) for a, b in zip(res2["centers"], res["centers"]))
+
+
 def test_random_init_with_unused_label_fails_validation(oracle, zoo):
     # la:28 + cf:146-172: L labels drawn at random; an unused label stops the chain.
     bad = None
