@@ -130,6 +130,14 @@ typedef struct {
      * the host continued from their first unfinished scan or update (an update the device handed
      * back, a draw outside the stream window) */
     int64_t sm_chain_runs, sm_chain_scans, sm_chain_resumes;
+    /* the early conditional go of the host update's pipeline: goes the host gave for a sweep
+     * enqueued ahead at the join of the speculated update, before the running sweep had ended
+     * (the wait kernel then decides from that sweep's control block, no host round trip);
+     * those behind which the device went, and those it declined (the running sweep moved
+     * points or needed another launch: the enqueued kernels gated themselves off).
+     * pipe_early == pipe_early_ran + pipe_early_off.  HDPM_PIPE_EARLY=0 in the environment
+     * (read once per process) leaves every go to the sweep's end, for A/B runs. */
+    int64_t pipe_early, pipe_early_ran, pipe_early_off;
 } hdpm_stats;
 
 int         hdpm_device_count(void);

@@ -892,21 +892,35 @@ struct Ctx {
     uint64_t gen[2] = {0, 0};          // window launches the kernels waited for
     std::chrono::steady_clock::time_point t_enq;   // the wait kernel was queued (pipe_go's deadline)
     bool au = false;                   // the wait kernel may give the go itself (PipeAuto)
+    bool early = false;                // the host gave its go at the join (pipe_early_go)
+    const uint32_t* early_raw = nullptr;   // ... with these draws
+    bool early_went = false;           // ... and the running sweep then ended quiet: the device goes (pipe_early_confirm)
   } pre;
   bool pipe_auto = true;               // device-side go for the device update's pipeline (HDPM_PIPE_AUTO=0: off)
-  // PipeAuto: the wait kernel's decision (1: it gave the go, 2: it waits for the host), once it
-  // has run (it runs once the previous sweep and the speculated update are done: microseconds)
+  // The wait kernel's decision where it makes the last part of it (PipeAuto, or after the early
+  // go of the host update's pipeline): 1 it went, 2 it did not (PipeAuto: it waits for the
+  // host's flag; early go: it gated the sweep off), once it has run (it runs once the previous
+  // sweep, and with PipeAuto the speculated update, are done: microseconds).  It writes the word
+  // before any wait of its own, so a word still unwritten after the limit means the stream is
+  // stuck or failed: the chain state is then no longer defined.
   int pre_dev_decision() {
-    if (!pre.active || !pre.au) return 0;
-    const int* w = &h_pipe.p[pre.par].dev;
+    if (!pre.active || !(pre.au || pre.early)) return 0;
+    return slot_dev_decision(pre.par);
+  }
+  int slot_dev_decision(int q) {
+    const int* w = &h_pipe.p[q].dev;
     const auto t0 = std::chrono::steady_clock::now();
     for (int polls = 0;; ++polls) {
       const int v = __atomic_load_n(w, __ATOMIC_ACQUIRE);
       if (v != 0) return v;
       HostPool::spin_pause();
       if ((polls & 1023) == 1023 && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(5)) {
-        // (the kernel behind the stream's work never ran: treat it as waiting for the flag)
-        return 2;
+        (void)hipStreamSynchronize(stream);
+        have_state = false;
+        err = "the wait kernel of a sweep enqueued ahead did not report its decision";
+        stats.pipe_desync++;
+        const int v2 = __atomic_load_n(w, __ATOMIC_ACQUIRE);
+        return v2 != 0 ? v2 : 2;
       }
     }
   }
@@ -943,6 +957,12 @@ struct Ctx {
   hipEvent_t ev_stage_buf[3] = {nullptr, nullptr, nullptr};
   int stage_fill = 0, stage_last = 1;   // buffer being filled / last committed
   int stage_hold = -1;                  // filled by the speculative update_phi, not yet committed
+  // A staging buffer that a sweep enqueued ahead scatters from in place (pre_enqueue) is busy
+  // until that sweep's round is resolved or the sweep is gated off: q + 1 for the round's
+  // control block q (its resolver event ev_res[q] is behind the scatter in stream order), 0
+  // free.  No marker of its own on the stream: an event record between the resolver and the next
+  // sweep's wait kernel is a ~5 us gap in the device's chain of sweeps.
+  int stage_pipe_busy[3] = {0, 0, 0};
   // the new tables of a full update_phi, committed after the next speculative update_phi is
   // started (flush_commit): buffer, entries
   // (dev: the speculative device update's tables, phd.stage)
@@ -1549,6 +1569,13 @@ struct Ctx {
       f = pick();
     }
     stage_fill = f;
+    if (stage_pipe_busy[f]) {
+      // (not yet seen resolved by the host: ev_res[q] is still that round's record)
+      const int q = stage_pipe_busy[f] - 1;
+      if (ev_res[q]) HIPCHK(hipEventSynchronize(ev_res[q]));
+      else HIPCHK(hipStreamSynchronize(stream));
+      stage_pipe_busy[f] = 0;
+    }
     hipEvent_t& ev = ev_stage_buf[stage_fill];
     if (!ev) HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
     HIPCHK(hipEventSynchronize(ev));                // the upload before last has left this buffer
@@ -2612,6 +2639,9 @@ struct Ctx {
     __atomic_store_n(&h_pipe.p[q].dev, 0, __ATOMIC_RELEASE);
     h_pipe.p[q].raw = nullptr;
     h_pipe.p[q].raw_dev = nullptr;
+    pre.early = false;
+    pre.early_raw = nullptr;
+    pre.early_went = false;
     // the next sweep's draws start after this update's (about a slice): the windows that
     // overlap that stretch (not a window generation started for later sweeps)
     const bool dev = !host_spec();
@@ -2684,10 +2714,57 @@ struct Ctx {
     summary_by_scatter = true;
     pre.round_ok = launch_round(0, K, m, nullptr, track, kRoundAll, &d_pipe.p[q], q) == kOk;
     summary_by_scatter = false;
-    // the staging buffer's release marker after the round, not between the scatter and the
-    // round's first kernel: an event record there cost the sweep a ~6 us gap
-    if (!dev) HIPCHK(hipEventRecord(ev_stage_buf[pre.buf], stream));
+    // the staging buffer is released by the host when it sees this round resolved
+    // (stage_pipe_busy): no marker between this round's resolver and the next wait kernel
+    if (!dev) stage_pipe_busy[pre.buf] = q + 1;
     stats.pipe_enqueued++;
+  }
+  // The host's go for the sweep just enqueued, given at the join of this iteration's speculated
+  // update -- before the running sweep has ended.  Everything pipe_go will test is host state
+  // that is known here, except "the running sweep completes in its one launch without a move",
+  // and that k_pipe_wait checks itself (the sweep's control block, final before it in stream
+  // order) and reports (PipeSlot::dev).  So the go is given only when, behind such a sweep,
+  // update_phi is certain to take the speculation whole (its use_spec / spec_layout tests, with
+  // moves == 0 and K unchanged) and pipe_go to agree; a device that went can then always be
+  // followed.  Any condition that cannot be shown here leaves the late go of pipe_go.
+  //   freq_before_ok: the host's frequency tables are those of the pre-sweep labels (they stay
+  //   current through a sweep without moves).
+  // The draws: the next sweep's start at spec.pos + spec.off[K], addressed in the window
+  // device_draws will pick (the earliest that covers them), which the enqueued kernels must
+  // have waited for; the chain's rng is not touched.
+  void pipe_early_go(int m, bool track, bool freq_before_ok) {
+    static const bool env_off = [] {
+      const char* e = std::getenv("HDPM_PIPE_EARLY");
+      return e && e[0] == '0';
+    }();
+    if (env_off || !pre.active || !pre.round_ok || pre.dev || pre.au || pre.m != m) return;
+    // (the gate-off test mode keeps its time-out; a recorded sweep's label download stays ahead
+    // of any sweep that writes d_c, as for PipeAuto in pre_enqueue)
+    if (!pipe_host_check || (record_now && !host_c_valid)) return;
+    const StreamAhead& sa = phi_stream;
+    // (deep_ok: iteration() defers this update's commit and calls pipe_go with this m)
+    if (!(deep_ok && host_spec() && !(debug & 128))) return;
+    if (!(spec.ran && spec.joined && K > 0 && spec.K == K && spec.nvalid == K)) return;
+    if (!(spec.pos == rng.pos && spec.epoch == rng.epoch && sa.n > 0 && sa.start.pos == spec.pos)) return;
+    if (!(spec.stage_buf >= 0 && spec.stage_buf == stage_hold && spec.stage_buf == pre.buf)) return;
+    if (!(track && freq_dev_valid && freq_before_ok)) return;
+    if (std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - pre.t_enq).count() >
+        (double)pipe_limit_ticks * 0.01 * 0.25)
+      return;
+    const uint64_t pos = spec.pos + (uint64_t)spec.off[K];
+    const int64_t len = (int64_t)n * (m + 1);
+    int wk = -1;
+    for (int k = 0; k < 2; ++k)
+      if (covers(win[k], pos, len) && (wk < 0 || win[k].start_pos < win[wk].start_pos)) wk = k;
+    if (wk < 0 || win[wk].gen != pre.gen[wk]) return;
+    const uint32_t* raw = win[wk].raw.p + (pos - win[wk].start_pos);
+    PipeSlot& sl = h_pipe.p[pre.par];
+    pre.early = true;
+    pre.early_raw = raw;
+    __atomic_store_n(&sl.raw, raw, __ATOMIC_RELAXED);
+    __atomic_store_n(&sl.flag, 1, __ATOMIC_RELEASE);
+    stats.pipe_early++;
+    mark("early_go");
   }
   void pre_release() {
     if (!pre.active) return;
@@ -2701,16 +2778,22 @@ struct Ctx {
     }
     pre.active = false;
     __atomic_store_n(&h_pipe.p[pre.par].flag, 2, __ATOMIC_RELEASE);
+    if (pre.buf >= 0) stage_pipe_busy[pre.buf] = 0;         // (a gated-off scatter reads nothing)
   }
   // Go for the sweep enqueued ahead: its draws reserved and handed over, its tables (the
   // update's held staging buffer) become the committed ones, the next speculative update
   // started.  False (nothing done) when it cannot run.
   bool pipe_go(int m) {
     // (PipeAuto: the wait kernel may have given the go itself; the host then follows it)
-    const bool went = pre_dev_decision() == 1;
+    // (the early go: the host read the decision off the sweep's control block in neal8_sweep)
+    const bool early = pre.active && pre.early;
+    const bool went = early ? pre.early_went : pre_dev_decision() == 1;
     const bool agree = pre.active && pre.round_ok && pre.m == m && commit_later.active && last_sweep_rounds == 1 &&
                        last_sweep_moves == 0 && !tables_dirty;
-    if (went && !(agree && pre.dev && commit_later.dev && freq_dev_valid && freq_version == labels_version)) {
+    // (after an early go: this update came whole from the host speculation the sweep scatters)
+    const bool same_tables = pre.dev ? (pre.au && commit_later.dev)
+                                     : (pre.early && !commit_later.dev && commit_later.buf == pre.buf && host_spec());
+    if (went && !(agree && same_tables && freq_dev_valid && freq_version == labels_version)) {
       (void)hipStreamSynchronize(stream);
       have_state = false;
       err = "a sweep went ahead on the device where the host would not have";
@@ -2737,7 +2820,17 @@ struct Ctx {
     const Rng saved = rng;
     const uint32_t* raw = device_draws((int64_t)n * (m + 1));
     PipeSlot& sl = h_pipe.p[pre.par];
-    if (went) {
+    if (went && early) {
+      // the draws handed over with the early go are the ones reserved now
+      if (raw != pre.early_raw) {
+        (void)hipStreamSynchronize(stream);
+        have_state = false;
+        err = "a sweep went ahead on the device with other draws than the host reserved";
+        stats.pipe_desync++;
+        pre.active = false;
+        return false;
+      }
+    } else if (went) {
       // the draws the device chose (the same stretch of the stream, in a window it waited for)
       raw = __atomic_load_n(&sl.raw_dev, __ATOMIC_ACQUIRE);
       stats.pipe_auto++;
@@ -2782,9 +2875,18 @@ struct Ctx {
       stage_full = true;
       if (stage_hold == pre.buf) stage_hold = -1;
       spec_launch();
+      if (early) pipe_early_confirm(pre.par);
     }
     mark("ahead.spec");
     return true;
+  }
+  // The wait kernel's own word behind an early go the host has followed: it must say "went".
+  void pipe_early_confirm(int q) {
+    if (slot_dev_decision(q) == 1 && have_state) return;
+    (void)hipStreamSynchronize(stream);
+    have_state = false;
+    err = "the host followed an early go that the device did not take";
+    stats.pipe_desync++;
   }
 
   int neal8_sweep(int m) {
@@ -2864,6 +2966,7 @@ struct Ctx {
     const bool track = (launched_ahead || ahead_prefix) ? ahead.track : (freq_dev_valid && !recount_only());
     if (!launched_ahead && !ahead_prefix) sweep_buffers(track, m);
     while (p < n) {
+      bool enqueued = false;             // the next sweep was enqueued in this round (pre_enqueue)
       if (!(launched_ahead && stats.rounds == rounds0)) {
         // round 0 after a prepared prefix: the resolver part only (same arguments)
         const int part = (ahead_prefix && stats.rounds == rounds0) ? kRoundResolve : kRoundAll;
@@ -2884,13 +2987,17 @@ struct Ctx {
             last_sweep_moves == 0 && !(debug & 4194304)) {
           pre_enqueue(m, track);
           mark("pre");
+          enqueued = true;
         }
         if (spec.ran) spec_join();
         else if (host_spec()) prefill_phi_stream();
+        if (enqueued) pipe_early_go(m, track, freq_before_ok);
       }
       mark("prefill");
       HIPCHK(hipEventSynchronize(ev_res[par]));
       mark("resolved");
+      for (int& b : stage_pipe_busy)
+        if (b == par + 1) b = 0;           // this round's scatter is done with its staging buffer
       const bool piped_round = ahead_piped && stats.rounds == rounds0;
       if (piped_round ? pre_timed[par] : round_timed) {
         float t1 = 0;
@@ -2909,6 +3016,32 @@ struct Ctx {
       }
       stats.rounds++;
       const ResolveCtl c = *ctl_at(par);
+      if (pre.active && pre.early && enqueued) {
+        // the early go: the wait kernel decides on this same control block, final since the
+        // resolver ended, so the host knows the decision without waiting for the kernel
+        if (!c.status && c.next >= n && !c.moves) {
+          // it goes.  Its word (PipeSlot::dev) is checked by pipe_go once the next speculation
+          // is started (pipe_early_confirm): the kernel takes ~8 us, which this thread -- on
+          // the path to that start -- does not wait for.
+          pre.early_went = true;
+          stats.pipe_early_ran++;
+        } else {
+          // it declines (this sweep moved points or needs another launch): the enqueued kernels
+          // gate themselves off, as after pre_release
+          const int dv = pre_dev_decision();
+          pre.active = false;
+          if (pre.buf >= 0) stage_pipe_busy[pre.buf] = 0;   // (a gated-off scatter reads nothing)
+          if (!have_state) return kArg;
+          if (dv == 1) {
+            (void)hipStreamSynchronize(stream);
+            have_state = false;
+            err = "a sweep went ahead on the device behind a sweep that was not quiet";
+            stats.pipe_desync++;
+            return kArg;
+          }
+          stats.pipe_early_off++;
+        }
+      }
       if (c.status == kPipeOff && piped_round) {
         // the sweep enqueued ahead was gated off on the device (its wait kernel's limit
         // passed before the host's go reached it): none of its kernels ran, the tables of
@@ -5014,6 +5147,7 @@ int Ctx::iteration(const hdpm_chain_params* p, int iter, int* idx_1_sm, int* acc
     if (early && launch_next && pipe_go(p->m)) prepared = true;
     else pre_release();
   }
+  if (!have_state) return kArg;                          // (a go the host could not follow: pipe_desync)
   if (!prepared && early && commit_later.active && freq_version == labels_version && !(debug & 4) && !tables_dirty) {
     prepare_next_sweep(p->m, launch_next);               // spec_launch, flush_commit, round 0
     prepared = true;

@@ -4357,7 +4357,10 @@ __global__ void k_pipe_wait(PipeSlot* slot, const ResolveCtl* prev, ResolveCtl* 
     const int64_t end =
         (int64_t)__hip_atomic_load(reinterpret_cast<const uint64_t*>(&au.chain->end), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     const int64_t r = end - au.win_start;
-    const bool ok = cok == 1 && c->status == 0 && c->next >= n && c->moves == 0 && r >= 0 && r + au.sweep_len <= au.win_count;
+    // (a host that already released this sweep -- flag 2 -- is not overtaken)
+    const int f0 = __hip_atomic_load(&slot->flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    const bool ok = f0 != 2 && cok == 1 && c->status == 0 && c->next >= n && c->moves == 0 && r >= 0 &&
+                    r + au.sweep_len <= au.win_count;
     if (ok) {
       const uint32_t* raw = au.win_raw + r;
       g->raw = raw;
@@ -4400,6 +4403,10 @@ __global__ void k_pipe_wait(PipeSlot* slot, const ResolveCtl* prev, ResolveCtl* 
     o->aborted = 0;
     o->uncertain = -1;
   }
+  // the decision, for a host that gave its go before it knew the previous sweep's outcome (the
+  // early go, engine.cpp pipe_early_go): 1 went, 2 declined.  (With PipeAuto the word already
+  // holds 2: "waits for the flag".)
+  if (!au.on) __hip_atomic_store(&slot->dev, ok ? 1 : 2, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 hipError_t launch_pipe_wait(PipeSlot* slot, const ResolveCtl* prev, ResolveCtl* own, int n, PipeGate* g,
                             long long limit, hipStream_t s, const PipeAuto& au) {

@@ -214,12 +214,17 @@ __device__ __forceinline__ bool pipe_gate(A& a) {
 // move and the update completed (its chain word), its draws in the window `win_*` after the
 // update's end, and tells the host (dev 1, raw_dev); otherwise it writes dev 2 and waits for
 // the host's flag as before.  The host follows a device go (pipe_go) and never releases it.
+//
+// Early conditional go (the host update_phi's pipeline): the host writes flag 1 as soon as its
+// own conditions hold (the speculated update joined whole), before the previous sweep has
+// ended; the wait kernel's own check of that sweep's control block is then the last part of
+// the decision, and it reports it (dev 1 went, 2 declined) for the host to follow.
 constexpr int kPipeOff = 10;   // ResolveCtl::status of an enqueued sweep that was gated off
 struct PipeSlot {
   int flag;
-  int dev;                     // written by k_pipe_wait with PipeAuto: 1 went, 2 waits for flag
+  int dev;                     // written by k_pipe_wait: 1 went, 2 declined (PipeAuto: waits for flag)
   const uint32_t* raw;
-  const uint32_t* raw_dev;     // the sweep's draws, when dev == 1
+  const uint32_t* raw_dev;     // the sweep's draws, when PipeAuto went
 };
 struct PhiChain;
 struct PipeAuto {
