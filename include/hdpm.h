@@ -380,6 +380,52 @@ int hdpm_trace_terms(hdpm_ctx* ctx, const int32_t* cls, int32_t ncand, uint64_t*
 int hdpm_trace_losses(hdpm_ctx* ctx, const int32_t* cls, int32_t ncand, double* vi_lb, double* vi,
                       uint64_t* binder_Q, uint64_t* binder_P);
 int hdpm_trace_tables(hdpm_ctx* ctx, const int32_t* cls, int32_t ncand, int32_t m0, int32_t nm, uint32_t* out);
+/* mcclust.ext minVI(method = "avg") / mcclust minbinder(method = "avgl") =
+ * hclust(as.dist(1 - psm), "average") + cutree, from the saved labels alone.  Points whose
+ * labels agree in every draw have psm = 1 (distance 0) and any other pair has distance
+ * >= 1/M, so average linkage merges each such group completely first; the rest of the tree
+ * is average linkage on the U distinct label columns, each weighted by its member count.
+ * The calls below are made in this order after hdpm_trace_build (which discards the groups
+ * and the tree of an earlier trace); out of order they return HDPM_E_ARG with a message.
+ *
+ * hdpm_trace_groups: replaces the zero-height part of hclust.  Groups the N points by their
+ *   M-label column, exactly (a hash places a column, a byte-for-byte comparison admits it),
+ *   and numbers the groups by ascending smallest member; *U = their count.  max_groups: 0
+ *   means HDPM_TRACE_GROUPS_DEFAULT, at most HDPM_TRACE_GROUPS_MAX (the host holds U x U
+ *   uint64 for the tree); more distinct columns than that stop the device pass and return
+ *   HDPM_E_ARG ("too unsettled").  hash_bits: 0 = the full 32-bit hash, 1..32 keep that many
+ *   bits (testing: forces collisions); no result depends on it.  HDPM_E_ARG if N^2 M does
+ *   not fit 63 bits (the tree's integer sums).
+ * hdpm_trace_group_info: first[U] (smallest member), weight[U] (member count), group_of[N],
+ *   counts[U x U] = S[u][v] = #{m: the groups' labels agree in draw m} (S[u][u] = M; the sum
+ *   of psm over the two groups' points is w_u w_v S_uv / M).  Any output may be NULL.
+ * hdpm_trace_avg_tree: replaces hclust(.., "average") above height 0.  With Q_AB =
+ *   sum_{u in A, v in B} w_u w_v S_uv (uint64) the merge order is the greedy one, decided in
+ *   exact integer arithmetic: among the active pairs with the largest Q_AB / (w_A w_B), the
+ *   pair whose smaller `first` is smallest, then whose larger `first` is smallest; the merged
+ *   cluster keeps the smaller `first`.  R's hclust tie order is unpinned here (R is absent),
+ *   as minVI's other conventions are.  merge[(U - 1) x 2]: the two clusters of each step,
+ *   each named by its member group with the smallest `first` (= its smallest group number),
+ *   column 0 the name the merged cluster keeps.  height[U - 1] = 1 - Q_AB / (M w_A w_B) as
+ *   doubles, for inspection only.  Either output may be NULL.
+ * hdpm_trace_cut_losses: replaces cutree + VI.lb / VI / binder of each cut.  The cut into k
+ *   clusters is the state after U - k merges; for k = k0 .. k0 + nk - 1 (1 <= k <=
+ *   min(U, 255): the trace tables hold at most 255 clusters) vi_lb[nk], vi[nk] and the
+ *   integers of Binder's loss A + (P - 2 Q) / M, binder_A[nk] and binder_Q[nk] (P from
+ *   hdpm_trace_losses), all from tables over the U weighted groups; every integer equals
+ *   what hdpm_trace_terms / hdpm_trace_losses give for the cut expanded to N labels.  Cuts
+ *   into more than U clusters split groups and never lower VI.lb.  Blocks of cuts obey
+ *   table_budget_bytes.  Any output may be NULL.
+ * hdpm_trace_cut_labels: cutree(k) per point, cl[N], labels 0..k-1 in order of first
+ *   appearance, 1 <= k <= U. */
+#define HDPM_TRACE_GROUPS_DEFAULT 8192
+#define HDPM_TRACE_GROUPS_MAX 16384
+int hdpm_trace_groups(hdpm_ctx* ctx, int32_t max_groups, int32_t hash_bits, int32_t* U);
+int hdpm_trace_group_info(hdpm_ctx* ctx, int32_t* first, int32_t* weight, int32_t* group_of, uint32_t* counts);
+int hdpm_trace_avg_tree(hdpm_ctx* ctx, int32_t* merge, double* height);
+int hdpm_trace_cut_losses(hdpm_ctx* ctx, int32_t k0, int32_t nk, double* vi_lb, double* vi, uint64_t* binder_A,
+                          uint64_t* binder_Q);
+int hdpm_trace_cut_labels(hdpm_ctx* ctx, int32_t k, int32_t* cl);
 /* Testing: one draw on the device from log-weights logw[E] (E <= 256) and the uniform rU --
  * the n8:95-102 categorical draw (two_way = 0; *pick = the 0-based index, or -status) or the
  * sm:204-215 two-way draw (two_way = 1, E = 2) -- with the engine's exp, glibc's algorithm

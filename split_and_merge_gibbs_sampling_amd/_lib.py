@@ -29,6 +29,8 @@ EXPORTS = (
     "hdpm_get_pool_heads", "hdpm_set_option", "hdpm_get_option", "hdpm_debug_draw", "hdpm_debug_math",
     "hdpm_psm_build", "hdpm_psm_rows", "hdpm_psm_vi_lb",
     "hdpm_trace_build", "hdpm_trace_terms", "hdpm_trace_losses", "hdpm_trace_tables",
+    "hdpm_trace_groups", "hdpm_trace_group_info", "hdpm_trace_avg_tree", "hdpm_trace_cut_losses",
+    "hdpm_trace_cut_labels",
 )
 
 OPT_HIG_LOGSPACE = 1
@@ -154,6 +156,11 @@ def lib():
         "hdpm_trace_terms": ([vp, vp, i32, vp, vp], C.c_int),
         "hdpm_trace_losses": ([vp, vp, i32, vp, vp, vp, vp], C.c_int),
         "hdpm_trace_tables": ([vp, vp, i32, i32, i32, vp], C.c_int),
+        "hdpm_trace_groups": ([vp, i32, i32, P(i32)], C.c_int),
+        "hdpm_trace_group_info": ([vp, vp, vp, vp, vp], C.c_int),
+        "hdpm_trace_avg_tree": ([vp, vp, vp], C.c_int),
+        "hdpm_trace_cut_losses": ([vp, i32, i32, vp, vp, vp, vp], C.c_int),
+        "hdpm_trace_cut_labels": ([vp, i32, vp], C.c_int),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name)

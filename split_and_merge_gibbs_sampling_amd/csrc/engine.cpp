@@ -36,6 +36,7 @@
 #include "mtjump.hpp"
 #include "pool_host.hpp"
 #include "rmath.hpp"
+#include "trace_tree.hpp"
 
 namespace hdpm {
 
@@ -84,6 +85,18 @@ hipError_t launch_tr_gather(const uint8_t* lab, const uint8_t* cls, int N, int N
                             hipStream_t s);
 hipError_t launch_tr_reduce(const uint32_t* tab, int ncand, int M, int cells, uint64_t* q1, double* l1, uint64_t* q,
                             double* l, hipStream_t s);
+hipError_t launch_tg_insert(const uint8_t* lab, int N, int Np, int M, int hash_bits, uint32_t tslots,
+                            uint32_t max_groups, uint32_t* rep, uint32_t* first, uint32_t* pslot, uint32_t* ctl,
+                            hipStream_t s);
+hipError_t launch_tg_finish(const uint8_t* lab, int N, int Np, int M, int U, int Mp, int Up, const uint32_t* pslot,
+                            const uint32_t* slot_gid, const uint32_t* first, uint32_t* group_of, uint32_t* weight,
+                            uint8_t* sig, uint8_t* sigT, hipStream_t s);
+hipError_t launch_tg_counts(const uint8_t* sig, int U, int M, int Mp, uint32_t* S, hipStream_t s);
+hipError_t launch_tg_tables(const uint8_t* sigT, const uint8_t* cut, const uint32_t* w, int U, int Up, int M, int ncut,
+                            int Ka, int Kz, uint32_t* tab, hipStream_t s);
+hipError_t launch_tg_gather(const uint8_t* sigT, const uint8_t* cut, int U, int Up, int M, int ncut, int Ka, int Kz,
+                            const uint32_t* tab, const uint32_t* sizes, uint64_t* all, uint64_t* same, hipStream_t s);
+hipError_t launch_tg_expand(const uint32_t* group_of, const int32_t* cut, int N, int32_t* cl, hipStream_t s);
 hipError_t launch_debug_draw(const double* logw, int E, double rU, int two_way, int ocml, int* out, hipStream_t s);
 hipError_t launch_debug_math(const double* x, int64_t n, int fn, int ocml, double* out, hipStream_t s);
 hipError_t launch_lmatrix(const uint8_t* codes_t, int n, int d, int nq, ParamTables cl, int K, double* L,
@@ -771,6 +784,18 @@ struct Ctx {
   size_t tr_budget = 0;
   uint64_t tr_P = 0;     // sum_m sum_b C2(n^m_b)
   double tr_S = 0.0;     // sum_m sum_b n^m_b log2 n^m_b
+  // groups of equal label columns and their average-linkage tree (hdpm_trace_groups ..
+  // hdpm_trace_cut_labels): the open-addressing table, group_of per point, the groups'
+  // signatures both ways round, S (U x U) once it is first needed, the tree on the host
+  DevBuf<uint32_t> d_tg_rep, d_tg_slotfirst, d_tg_pslot, d_tg_ctl, d_tg_slotgid, d_tg_of, d_tg_first, d_tg_w, d_tg_S;
+  DevBuf<uint8_t> d_tg_sig, d_tg_sigT, d_tg_cut;
+  DevBuf<uint64_t> d_tg_all, d_tg_same;
+  DevBuf<int32_t> d_tg_cl, d_tg_cutw;
+  int tg_U = 0, tg_Mp = 0, tg_Up = 0;
+  bool tg_counts = false, tg_tree = false;
+  std::vector<uint32_t> tg_first, tg_w;
+  std::vector<int32_t> tg_merge;
+  std::vector<double> tg_height;
 
   Rng rng;
 
@@ -5797,6 +5822,8 @@ int hdpm_trace_build(hdpm_ctx* h, const int32_t* c_trace, int32_t M, int32_t N, 
   }
   GUARD({
     ctx->tr_N = 0;   // no trace until this one is complete
+    ctx->tg_U = 0;   // and no groups or tree of the previous one
+    ctx->tg_counts = ctx->tg_tree = false;
     const int Np = (int)(((int64_t)N + 15) & ~(int64_t)15);
     ctx->d_tr_lab.ensure((size_t)M * Np);
     ctx->d_tr_sizes.ensure((size_t)M * 256);
@@ -5939,6 +5966,249 @@ int hdpm_trace_tables(hdpm_ctx* h, const int32_t* cls, int32_t ncand, int32_t m0
                         (size_t)Kz * 4);
       }
     });
+    return HDPM_OK;
+  })
+}
+// ---- average-linkage search on the groups of equal label columns (trace_summary.hip k_tg_*,
+// trace_tree.hpp)
+static int tg_need(Ctx* ctx, bool tree) {
+  if (ctx->tr_N == 0) { ctx->err = "trace: hdpm_trace_build has not been called"; return HDPM_E_ARG; }
+  if (ctx->tg_U == 0) { ctx->err = "trace: hdpm_trace_groups has not been called"; return HDPM_E_ARG; }
+  if (tree && !ctx->tg_tree) { ctx->err = "trace: hdpm_trace_avg_tree has not been called"; return HDPM_E_ARG; }
+  return HDPM_OK;
+}
+static void tg_counts(Ctx* ctx) {
+  if (ctx->tg_counts) return;
+  const size_t U = (size_t)ctx->tg_U;
+  ctx->d_tg_S.ensure(U * U);
+  HIPCHK(hdpm::launch_tg_counts(ctx->d_tg_sig.p, ctx->tg_U, ctx->tr_M, ctx->tg_Mp, ctx->d_tg_S.p, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  ctx->tg_counts = true;
+}
+int hdpm_trace_groups(hdpm_ctx* h, int32_t max_groups, int32_t hash_bits, int32_t* U_out) {
+  CTX();
+  if (ctx->tr_N == 0) { ctx->err = "trace: hdpm_trace_build has not been called"; return HDPM_E_ARG; }
+  if (max_groups == 0) max_groups = HDPM_TRACE_GROUPS_DEFAULT;
+  if (max_groups < 0 || max_groups > HDPM_TRACE_GROUPS_MAX || hash_bits < 0 || hash_bits > 32) {
+    ctx->err = "trace: max_groups must be in 1.." + std::to_string(HDPM_TRACE_GROUPS_MAX) + " and hash_bits in 0..32";
+    return HDPM_E_ARG;
+  }
+  const int N = ctx->tr_N, Np = ctx->tr_Np, M = ctx->tr_M;
+  if ((unsigned __int128)N * (unsigned __int128)N * (unsigned __int128)M >> 63) {
+    ctx->err = "trace: N^2 M does not fit 63 bits: the tree's integer sums would overflow";
+    return HDPM_E_ARG;
+  }
+  GUARD({
+    ctx->tg_U = 0;
+    ctx->tg_counts = ctx->tg_tree = false;
+    uint32_t T = 1024;
+    while (T < 4u * (uint32_t)max_groups) T <<= 1;
+    ctx->d_tg_rep.ensure(T);
+    ctx->d_tg_slotfirst.ensure(T);
+    ctx->d_tg_slotgid.ensure(T);
+    ctx->d_tg_pslot.ensure((size_t)N);
+    ctx->d_tg_ctl.ensure(2);
+    HIPCHK(hipMemsetAsync(ctx->d_tg_rep.p, 0xFF, (size_t)T * 4, ctx->stream));
+    HIPCHK(hipMemsetAsync(ctx->d_tg_slotfirst.p, 0xFF, (size_t)T * 4, ctx->stream));
+    HIPCHK(hipMemsetAsync(ctx->d_tg_ctl.p, 0, 8, ctx->stream));
+    HIPCHK(hdpm::launch_tg_insert(ctx->d_tr_lab.p, N, Np, M, hash_bits, T, (uint32_t)max_groups, ctx->d_tg_rep.p,
+                                  ctx->d_tg_slotfirst.p, ctx->d_tg_pslot.p, ctx->d_tg_ctl.p, ctx->stream));
+    uint32_t ctl[2] = {0u, 0u};
+    std::vector<uint32_t> sf((size_t)T);
+    HIPCHK(hipMemcpyAsync(ctl, ctx->d_tg_ctl.p, 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(sf.data(), ctx->d_tg_slotfirst.p, (size_t)T * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    if (ctl[1]) {
+      ctx->err = "trace: more than max_groups = " + std::to_string(max_groups) +
+                 " distinct label columns: the trace is too unsettled for the average-linkage search";
+      return HDPM_E_ARG;
+    }
+    // the groups numbered by ascending smallest member: whichever slot a column landed in
+    std::vector<std::pair<uint32_t, uint32_t>> order;
+    for (uint32_t s = 0; s < T; ++s)
+      if (sf[s] != 0xFFFFFFFFu) order.emplace_back(sf[s], s);
+    std::sort(order.begin(), order.end());
+    const int U = (int)order.size();
+    if (U == 0 || (uint32_t)U != ctl[0]) { ctx->err = "trace: the group table is inconsistent"; return HDPM_E_DEVICE; }
+    std::vector<uint32_t> gid((size_t)T, 0u);
+    ctx->tg_first.resize((size_t)U);
+    for (int u = 0; u < U; ++u) {
+      ctx->tg_first[u] = order[u].first;
+      gid[order[u].second] = (uint32_t)u;
+    }
+    const int Mp = (M + 63) & ~63, Up = (U + 15) & ~15;
+    ctx->d_tg_of.ensure((size_t)N);
+    ctx->d_tg_first.ensure((size_t)U);
+    ctx->d_tg_w.ensure((size_t)U);
+    ctx->d_tg_sig.ensure((size_t)U * Mp);
+    ctx->d_tg_sigT.ensure((size_t)M * Up);
+    HIPCHK(hipMemcpyAsync(ctx->d_tg_slotgid.p, gid.data(), (size_t)T * 4, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(ctx->d_tg_first.p, ctx->tg_first.data(), (size_t)U * 4, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemsetAsync(ctx->d_tg_w.p, 0, (size_t)U * 4, ctx->stream));
+    HIPCHK(hdpm::launch_tg_finish(ctx->d_tr_lab.p, N, Np, M, U, Mp, Up, ctx->d_tg_pslot.p, ctx->d_tg_slotgid.p,
+                                  ctx->d_tg_first.p, ctx->d_tg_of.p, ctx->d_tg_w.p, ctx->d_tg_sig.p, ctx->d_tg_sigT.p,
+                                  ctx->stream));
+    ctx->tg_w.resize((size_t)U);
+    HIPCHK(hipMemcpyAsync(ctx->tg_w.data(), ctx->d_tg_w.p, (size_t)U * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    ctx->tg_Mp = Mp;
+    ctx->tg_Up = Up;
+    ctx->tg_U = U;
+    if (U_out) *U_out = U;
+    return HDPM_OK;
+  })
+}
+int hdpm_trace_group_info(hdpm_ctx* h, int32_t* first, int32_t* weight, int32_t* group_of, uint32_t* counts) {
+  CTX();
+  if (int st = tg_need(ctx, false)) return st;
+  GUARD({
+    const size_t U = (size_t)ctx->tg_U;
+    if (first) std::memcpy(first, ctx->tg_first.data(), U * 4);
+    if (weight) std::memcpy(weight, ctx->tg_w.data(), U * 4);
+    if (group_of)
+      HIPCHK(hipMemcpyAsync(group_of, ctx->d_tg_of.p, (size_t)ctx->tr_N * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (counts) {
+      tg_counts(ctx);
+      HIPCHK(hipMemcpyAsync(counts, ctx->d_tg_S.p, U * U * 4, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return HDPM_OK;
+  })
+}
+int hdpm_trace_avg_tree(hdpm_ctx* h, int32_t* merge, double* height) {
+  CTX();
+  if (int st = tg_need(ctx, false)) return st;
+  GUARD({
+    const size_t U = (size_t)ctx->tg_U;
+    if (!ctx->tg_tree) {
+      tg_counts(ctx);
+      std::vector<uint32_t> S(U * U);
+      HIPCHK(hipMemcpyAsync(S.data(), ctx->d_tg_S.p, U * U * 4, hipMemcpyDeviceToHost, ctx->stream));
+      HIPCHK(hipStreamSynchronize(ctx->stream));
+      std::vector<uint64_t> w(ctx->tg_w.begin(), ctx->tg_w.end()), first(ctx->tg_first.begin(), ctx->tg_first.end());
+      ctx->tg_merge.assign((U - 1) * 2, 0);
+      ctx->tg_height.assign(U - 1, 0.0);
+      hdpm::tt_avg_linkage((int)U, w.data(), first.data(), S.data(), (uint64_t)ctx->tr_M, ctx->tg_merge.data(),
+                           ctx->tg_height.data());
+      ctx->tg_tree = true;
+    }
+    if (merge && U > 1) std::memcpy(merge, ctx->tg_merge.data(), (U - 1) * 2 * 4);
+    if (height && U > 1) std::memcpy(height, ctx->tg_height.data(), (U - 1) * 8);
+    return HDPM_OK;
+  })
+}
+int hdpm_trace_cut_losses(hdpm_ctx* h, int32_t k0, int32_t nk, double* vi_lb, double* vi, uint64_t* binder_A,
+                          uint64_t* binder_Q) {
+  CTX();
+  if (int st = tg_need(ctx, true)) return st;
+  if (k0 < 1 || nk < 1 || (int64_t)k0 + nk - 1 > std::min(ctx->tg_U, 255)) {
+    ctx->err = "trace: cuts k0 .. k0 + nk - 1 must lie in 1 .. min(U, 255)";
+    return HDPM_E_ARG;
+  }
+  GUARD({
+    const int N = ctx->tr_N, M = ctx->tr_M, Kz = ctx->tr_Kz, U = ctx->tg_U, Up = ctx->tg_Up, Ka = k0 + nk - 1;
+    const double dM = (double)M;
+    if (!vi_lb && !vi && !binder_A && !binder_Q) return HDPM_OK;
+    const bool reduce = vi || binder_Q;
+    const size_t per = (size_t)M * Ka * Kz;
+    size_t cb = std::max<size_t>(1, ctx->tr_budget / (per * 4));
+    cb = std::min(std::min(cb, kTraceMaxBlock), (size_t)nk);
+    ctx->d_tg_cut.ensure(cb * Up);
+    ctx->d_tr_tab.ensure(cb * per);
+    if (vi_lb) {
+      ctx->d_tg_all.ensure((size_t)U);
+      ctx->d_tg_same.ensure(cb * U);
+    }
+    if (reduce) {
+      ctx->d_tr_q1.ensure(cb * M);
+      ctx->d_tr_l1.ensure(cb * M);
+      ctx->d_tr_q.ensure(cb);
+      ctx->d_tr_l.ensure(cb);
+    }
+    std::vector<uint8_t> bytes(cb * Up);
+    std::vector<int32_t> cut((size_t)U);
+    std::vector<uint64_t> all, same, q, sz((size_t)Ka);
+    std::vector<double> lall, l, lsz((size_t)Ka);
+    for (int c0 = 0; c0 < nk; c0 += (int)cb) {
+      const int nc = std::min((int)cb, nk - c0);
+      std::memset(bytes.data(), 0xFF, bytes.size());
+      for (int c = 0; c < nc; ++c) {
+        hdpm::tt_cut(U, ctx->tg_merge.data(), k0 + c0 + c, cut.data());
+        for (int u = 0; u < U; ++u) bytes[(size_t)c * Up + u] = (uint8_t)cut[u];
+      }
+      HIPCHK(hipMemcpyAsync(ctx->d_tg_cut.p, bytes.data(), (size_t)nc * Up, hipMemcpyHostToDevice, ctx->stream));
+      HIPCHK(hipMemsetAsync(ctx->d_tr_tab.p, 0, (size_t)nc * per * 4, ctx->stream));
+      HIPCHK(hdpm::launch_tg_tables(ctx->d_tg_sigT.p, ctx->d_tg_cut.p, ctx->d_tg_w.p, U, Up, M, nc, Ka, Kz,
+                                    ctx->d_tr_tab.p, ctx->stream));
+      if (vi_lb) {
+        HIPCHK(hdpm::launch_tg_gather(ctx->d_tg_sigT.p, ctx->d_tg_cut.p, U, Up, M, nc, Ka, Kz, ctx->d_tr_tab.p,
+                                      ctx->d_tr_sizes.p, c0 == 0 ? ctx->d_tg_all.p : nullptr, ctx->d_tg_same.p,
+                                      ctx->stream));
+        if (c0 == 0) {
+          all.resize((size_t)U);
+          HIPCHK(hipMemcpyAsync(all.data(), ctx->d_tg_all.p, (size_t)U * 8, hipMemcpyDeviceToHost, ctx->stream));
+        }
+        same.resize((size_t)nc * U);
+        HIPCHK(hipMemcpyAsync(same.data(), ctx->d_tg_same.p, same.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+      }
+      if (reduce) {
+        HIPCHK(hdpm::launch_tr_reduce(ctx->d_tr_tab.p, nc, M, Ka * Kz, ctx->d_tr_q1.p, ctx->d_tr_l1.p, ctx->d_tr_q.p,
+                                      ctx->d_tr_l.p, ctx->stream));
+        q.resize((size_t)nc);
+        l.resize((size_t)nc);
+        HIPCHK(hipMemcpyAsync(q.data(), ctx->d_tr_q.p, (size_t)nc * 8, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipMemcpyAsync(l.data(), ctx->d_tr_l.p, (size_t)nc * 8, hipMemcpyDeviceToHost, ctx->stream));
+      }
+      HIPCHK(hipStreamSynchronize(ctx->stream));
+      if (vi_lb && c0 == 0) {
+        lall.resize((size_t)U);
+        for (int u = 0; u < U; ++u) lall[u] = std::log2((double)all[u] / dM);
+      }
+      for (int c = 0; c < nc; ++c) {
+        const uint8_t* cl = bytes.data() + (size_t)c * Up;
+        std::fill(sz.begin(), sz.end(), 0);
+        for (int u = 0; u < U; ++u) sz[cl[u]] += ctx->tg_w[u];
+        for (int a = 0; a < Ka; ++a) lsz[a] = sz[a] > 0 ? std::log2((double)sz[a]) : 0.0;
+        if (vi_lb) {
+          // the per-point term of hdpm_trace_losses, once per group and weighted by its size
+          const uint64_t* sm = same.data() + (size_t)c * U;
+          long double f = 0.0L;
+          for (int u = 0; u < U; ++u) {
+            const double term = (lsz[cl[u]] + lall[u] - 2 * std::log2((double)sm[u] / dM)) / N;
+            f += (long double)ctx->tg_w[u] * (long double)term;
+          }
+          vi_lb[c0 + c] = (double)f;
+        }
+        if (vi) {
+          double hc = 0.0;
+          for (int a = 0; a < Ka; ++a) hc = hc + (double)sz[a] * lsz[a];
+          vi[c0 + c] = (hc + (ctx->tr_S - 2 * l[c]) / dM) / N;
+        }
+        if (binder_A) {
+          uint64_t A = 0;
+          for (int a = 0; a < Ka; ++a) A += sz[a] * (sz[a] - (sz[a] > 0 ? 1 : 0)) / 2;
+          binder_A[c0 + c] = A;
+        }
+        if (binder_Q) binder_Q[c0 + c] = q[c];
+      }
+    }
+    return HDPM_OK;
+  })
+}
+int hdpm_trace_cut_labels(hdpm_ctx* h, int32_t k, int32_t* cl) {
+  CTX();
+  if (int st = tg_need(ctx, true)) return st;
+  if (!cl || k < 1 || k > ctx->tg_U) { ctx->err = "trace: the cut k must lie in 1 .. U"; return HDPM_E_ARG; }
+  GUARD({
+    const int N = ctx->tr_N, U = ctx->tg_U;
+    std::vector<int32_t> cut((size_t)U);
+    hdpm::tt_cut(U, ctx->tg_merge.data(), k, cut.data());
+    ctx->d_tg_cutw.ensure((size_t)U);
+    ctx->d_tg_cl.ensure((size_t)N);
+    HIPCHK(hipMemcpyAsync(ctx->d_tg_cutw.p, cut.data(), (size_t)U * 4, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hdpm::launch_tg_expand(ctx->d_tg_of.p, ctx->d_tg_cutw.p, N, ctx->d_tg_cl.p, ctx->stream));
+    HIPCHK(hipMemcpyAsync(cl, ctx->d_tg_cl.p, (size_t)N * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
     return HDPM_OK;
   })
 }

@@ -291,4 +291,286 @@ hipError_t launch_tr_reduce(const uint32_t* tab, int ncand, int M, int cells, ui
   return hipGetLastError();
 }
 
+// ------------------------------------------------- groups of equal label columns (k_tg_*)
+//
+// minVI(method = "avg") / minbinder(method = "avgl") without the matrix: points whose labels
+// agree in every draw have psm = 1 and merge first under average linkage, so the tree is
+// built on the U distinct label columns, each weighted by its member count (trace_tree.hpp).
+//
+//   k_tg_insert   hash of every point's M-byte column (4 points per thread, points fastest),
+//                 then an open-addressing insert: a point joins a slot only after its whole
+//                 column equals the slot's representative byte for byte, else it probes on
+//   k_tg_assign   group_of[i] and the member counts, once the host has numbered the slots
+//                 by ascending smallest member
+//   k_tg_sig      sig[U][Mp] (group-major, for the counts) and sigT[M][Up] (draw-major, a
+//                 trace of U weighted points for the tables) from the smallest members
+//   k_tg_counts   S[u][v] = #{m: sig_u[m] == sig_v[m]}: 64 x 64 outputs per workgroup, M in
+//                 slabs of 64 bytes through LDS, 4 x 4 outputs per thread, four bytes per
+//                 xor + zero-byte count
+//   k_tg_tables   T^m[a][b] = sum_u w_u [cut(u) = a][sig_u[m] = b] in the layout of k_tr_tables
+//   k_tg_gather   per group: sum_m n^m[sig_u[m]] and, per cut, sum_m T^m[cut(u)][sig_u[m]]
+//   k_tg_expand   a cut of the groups to labels per point
+//
+// The slot a column lands in depends on the insertion order; nothing else does: a column is
+// claimed by exactly one slot (its probe sequence is fixed and slots never empty), the
+// smallest member is an atomicMin, and the groups are numbered by that.
+
+constexpr uint32_t kTgEmpty = 0xFFFFFFFFu;
+constexpr int kTgTile = 64;      // outputs of k_tg_counts per workgroup, each way
+constexpr int kTgSlab = 64;      // bytes of M per LDS slab: Mp is a multiple
+constexpr int kTgLd = 17;        // words per LDS row (16 + 1: rows on different banks)
+
+__device__ __forceinline__ uint32_t tg_mix(uint32_t h) {
+  h ^= h >> 16;
+  h *= 0x85EBCA6Bu;
+  h ^= h >> 13;
+  h *= 0xC2B2AE35u;
+  h ^= h >> 16;
+  return h;
+}
+
+// rep / first: tmask + 1 slots, both 0xFF.. before the launch.  ctl[0] counts the slots
+// claimed; ctl[1] is set when more than max_groups are (or the table is full) and stops
+// every thread at its next point.
+__global__ __launch_bounds__(kTrThreads) void k_tg_insert(const uint8_t* __restrict__ lab, int N, int Np, int M,
+                                                         uint32_t hmask, uint32_t tmask, uint32_t max_groups,
+                                                         uint32_t* rep, uint32_t* first, uint32_t* __restrict__ pslot,
+                                                         uint32_t* ctl) {
+  const int p = (blockIdx.x * kTrThreads + threadIdx.x) * 4;
+  if (p >= N) return;
+  uint32_t h[4] = {2166136261u, 2166136261u, 2166136261u, 2166136261u};
+  for (int m = 0; m < M; ++m) {
+    const uint32_t zw = *(const uint32_t*)(lab + (int64_t)m * Np + p);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) h[k] = (h[k] ^ ((zw >> (8 * k)) & 0xFFu)) * 16777619u;
+  }
+  for (int k = 0; k < 4; ++k) {
+    const uint32_t i = (uint32_t)(p + k);
+    if (i >= (uint32_t)N) return;
+    if (__atomic_load_n(&ctl[1], __ATOMIC_RELAXED)) return;
+    uint32_t slot = tg_mix(h[k]) & hmask & tmask;
+    bool placed = false;
+    for (uint32_t probe = 0; probe <= tmask; ++probe, slot = (slot + 1u) & tmask) {
+      uint32_t r = __atomic_load_n(&rep[slot], __ATOMIC_RELAXED);
+      if (r == kTgEmpty) {
+        r = atomicCAS(&rep[slot], kTgEmpty, i);
+        if (r == kTgEmpty) {
+          if (atomicAdd(&ctl[0], 1u) >= max_groups) {
+            atomicExch(&ctl[1], 1u);
+            return;
+          }
+          r = i;
+        }
+      }
+      bool eq = true;
+      if (r != i)
+        for (int m = 0; m < M; ++m)
+          if (lab[(int64_t)m * Np + i] != lab[(int64_t)m * Np + r]) {
+            eq = false;
+            break;
+          }
+      if (eq) {
+        if (i < __atomic_load_n(&first[slot], __ATOMIC_RELAXED)) atomicMin(&first[slot], i);
+        pslot[i] = slot;
+        placed = true;
+        break;
+      }
+    }
+    if (!placed) {
+      atomicExch(&ctl[1], 1u);
+      return;
+    }
+  }
+}
+
+// weight (U) must be zero
+__global__ __launch_bounds__(kTrThreads) void k_tg_assign(const uint32_t* __restrict__ pslot,
+                                                         const uint32_t* __restrict__ slot_gid, int N,
+                                                         uint32_t* __restrict__ group_of, uint32_t* weight) {
+  const int i = blockIdx.x * kTrThreads + threadIdx.x;
+  if (i >= N) return;
+  const uint32_t g = slot_gid[pslot[i]];
+  group_of[i] = g;
+  atomicAdd(&weight[g], 1u);
+}
+
+// one thread per (group, draw) of the padded arrays: bytes beyond U or M are 0
+__global__ __launch_bounds__(kTrThreads) void k_tg_sig(const uint8_t* __restrict__ lab, int Np, int M, int U, int Mp,
+                                                      int Up, const uint32_t* __restrict__ first,
+                                                      uint8_t* __restrict__ sig, uint8_t* __restrict__ sigT) {
+  const int64_t t = (int64_t)blockIdx.x * kTrThreads + threadIdx.x;
+  if (t >= (int64_t)Up * Mp) return;
+  const int u = (int)(t % Up), m = (int)(t / Up);
+  const uint8_t b = (u < U && m < M) ? lab[(int64_t)m * Np + first[u]] : (uint8_t)0;
+  if (u < U) sig[(int64_t)u * Mp + m] = b;
+  if (m < M) sigT[(int64_t)m * Up + u] = b;
+}
+
+// zero bytes of x, four at a time
+__device__ __forceinline__ uint32_t tg_zero_bytes(uint32_t x) {
+  uint32_t t = (x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu;
+  t = ~(t | x | 0x7F7F7F7Fu);
+  return (uint32_t)__popc(t);
+}
+
+// `pad` = Mp - M: the padding bytes are 0 in every row and count as matches
+__global__ __launch_bounds__(kTrThreads) void k_tg_counts(const uint8_t* __restrict__ sig, int U, int Mp, uint32_t pad,
+                                                         uint32_t* __restrict__ S) {
+  __shared__ uint32_t A[kTgTile * kTgLd], B[kTgTile * kTgLd];
+  const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
+  const int u0 = blockIdx.y * kTgTile, v0 = blockIdx.x * kTgTile;
+  const int lr = tid >> 2, lq = (tid & 3) * 4;     // the row and first word this thread loads
+  uint32_t acc[4][4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[i][j] = 0u;
+  for (int s = 0; s < Mp; s += kTgSlab) {
+    uint4 a = make_uint4(0u, 0u, 0u, 0u), b = a;
+    if (u0 + lr < U) a = *(const uint4*)(sig + (int64_t)(u0 + lr) * Mp + s + lq * 4);
+    if (v0 + lr < U) b = *(const uint4*)(sig + (int64_t)(v0 + lr) * Mp + s + lq * 4);
+    uint32_t* ar = A + lr * kTgLd + lq;
+    uint32_t* br = B + lr * kTgLd + lq;
+    ar[0] = a.x; ar[1] = a.y; ar[2] = a.z; ar[3] = a.w;
+    br[0] = b.x; br[1] = b.y; br[2] = b.z; br[3] = b.w;
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < kTgSlab / 4; ++k) {
+      uint32_t av[4], bv[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        av[i] = A[(ty + 16 * i) * kTgLd + k];
+        bv[i] = B[(tx + 16 * i) * kTgLd + k];
+      }
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] += tg_zero_bytes(av[i] ^ bv[j]);
+    }
+    __syncthreads();
+  }
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int u = u0 + ty + 16 * i, v = v0 + tx + 16 * j;
+      if (u < U && v < U) S[(int64_t)u * U + v] = acc[i][j] - pad;
+    }
+}
+
+// One workgroup per (draw, cut): the table in LDS when Ka x Kz words fit (lds != 0), else
+// added straight to the global table.  tab must be zero.
+__global__ __launch_bounds__(kTrThreads) void k_tg_tables(const uint8_t* __restrict__ sigT,
+                                                         const uint8_t* __restrict__ cut,
+                                                         const uint32_t* __restrict__ w, int U, int Up, int M, int Ka,
+                                                         int Kz, int lds, uint32_t* tab) {
+  extern __shared__ __align__(16) uint32_t tr_lds[];
+  const int m = blockIdx.x, c = blockIdx.y, cells = Ka * Kz;
+  uint32_t* T = tab + ((int64_t)c * M + m) * cells;
+  if (lds) {
+    for (int q = threadIdx.x; q < cells; q += kTrThreads) tr_lds[q] = 0u;
+    __syncthreads();
+  }
+  uint32_t* dst = lds ? tr_lds : T;
+  for (int u = threadIdx.x; u < U; u += kTrThreads) {
+    const int a = cut[(int64_t)c * Up + u], b = sigT[(int64_t)m * Up + u];
+    if (a < Ka && b < Kz) atomicAdd(&dst[a * Kz + b], w[u]);
+  }
+  if (lds) {
+    __syncthreads();
+    for (int q = threadIdx.x; q < cells; q += kTrThreads)
+      if (tr_lds[q]) T[q] = tr_lds[q];
+  }
+}
+
+// blockIdx.y = cut of the block; blockIdx.y == ncut (launched only when `all` is wanted)
+// sums the draws' cluster sizes instead
+__global__ __launch_bounds__(kTrThreads) void k_tg_gather(const uint8_t* __restrict__ sigT,
+                                                         const uint8_t* __restrict__ cut, int U, int Up, int M,
+                                                         int ncut, int Ka, int Kz, const uint32_t* __restrict__ tab,
+                                                         const uint32_t* __restrict__ sizes,
+                                                         unsigned long long* __restrict__ all,
+                                                         unsigned long long* __restrict__ same) {
+  const int u = blockIdx.x * kTrThreads + threadIdx.x;
+  if (u >= U) return;
+  const int c = blockIdx.y;
+  unsigned long long acc = 0ull;
+  if (c == ncut) {
+    for (int m = 0; m < M; ++m) {
+      const uint32_t b = sigT[(int64_t)m * Up + u];
+      if (b != 0xFFu) acc += sizes[(int64_t)m * 256 + b];
+    }
+    all[u] = acc;
+    return;
+  }
+  const int a = cut[(int64_t)c * Up + u];
+  const uint32_t* T = tab + (int64_t)c * M * Ka * Kz;
+  if (a < Ka)
+    for (int m = 0; m < M; ++m) {
+      const int b = sigT[(int64_t)m * Up + u];
+      if (b < Kz) acc += T[((int64_t)m * Ka + a) * Kz + b];
+    }
+  same[(int64_t)c * U + u] = acc;
+}
+
+__global__ __launch_bounds__(kTrThreads) void k_tg_expand(const uint32_t* __restrict__ group_of,
+                                                         const int32_t* __restrict__ cut, int N,
+                                                         int32_t* __restrict__ cl) {
+  const int i = blockIdx.x * kTrThreads + threadIdx.x;
+  if (i < N) cl[i] = cut[group_of[i]];
+}
+
+// rep / first (tslots each) must be 0xFF.., ctl (2 words) zero; tslots a power of two
+hipError_t launch_tg_insert(const uint8_t* lab, int N, int Np, int M, int hash_bits, uint32_t tslots,
+                            uint32_t max_groups, uint32_t* rep, uint32_t* first, uint32_t* pslot, uint32_t* ctl,
+                            hipStream_t s) {
+  const uint32_t hmask = hash_bits <= 0 || hash_bits >= 32 ? 0xFFFFFFFFu : (1u << hash_bits) - 1u;
+  const int nb = (((N + 3) >> 2) + kTrThreads - 1) / kTrThreads;
+  hipLaunchKernelGGL(k_tg_insert, dim3(nb), dim3(kTrThreads), 0, s, lab, N, Np, M, hmask, tslots - 1u, max_groups, rep,
+                     first, pslot, ctl);
+  return hipGetLastError();
+}
+
+// weight (U) must be zero; sig is U x Mp, sigT is M x Up
+hipError_t launch_tg_finish(const uint8_t* lab, int N, int Np, int M, int U, int Mp, int Up, const uint32_t* pslot,
+                            const uint32_t* slot_gid, const uint32_t* first, uint32_t* group_of, uint32_t* weight,
+                            uint8_t* sig, uint8_t* sigT, hipStream_t s) {
+  hipLaunchKernelGGL(k_tg_assign, dim3((N + kTrThreads - 1) / kTrThreads), dim3(kTrThreads), 0, s, pslot, slot_gid, N,
+                     group_of, weight);
+  const int64_t tot = (int64_t)Up * Mp;
+  hipLaunchKernelGGL(k_tg_sig, dim3((unsigned)((tot + kTrThreads - 1) / kTrThreads)), dim3(kTrThreads), 0, s, lab, Np,
+                     M, U, Mp, Up, first, sig, sigT);
+  return hipGetLastError();
+}
+
+hipError_t launch_tg_counts(const uint8_t* sig, int U, int M, int Mp, uint32_t* S, hipStream_t s) {
+  const int nt = (U + kTgTile - 1) / kTgTile;
+  hipLaunchKernelGGL(k_tg_counts, dim3(nt, nt), dim3(kTrThreads), 0, s, sig, U, Mp, (uint32_t)(Mp - M), S);
+  return hipGetLastError();
+}
+
+// tab (ncut x M x Ka x Kz) must be zero; cut is ncut x Up bytes
+hipError_t launch_tg_tables(const uint8_t* sigT, const uint8_t* cut, const uint32_t* w, int U, int Up, int M, int ncut,
+                            int Ka, int Kz, uint32_t* tab, hipStream_t s) {
+  const int lds = Ka * Kz <= kTrLdsWords ? 1 : 0;
+  hipLaunchKernelGGL(k_tg_tables, dim3(M, ncut), dim3(kTrThreads), lds ? (size_t)Ka * Kz * 4 : 0, s, sigT, cut, w, U,
+                     Up, M, Ka, Kz, lds, tab);
+  return hipGetLastError();
+}
+
+hipError_t launch_tg_gather(const uint8_t* sigT, const uint8_t* cut, int U, int Up, int M, int ncut, int Ka, int Kz,
+                            const uint32_t* tab, const uint32_t* sizes, uint64_t* all, uint64_t* same, hipStream_t s) {
+  const int ny = ncut + (all ? 1 : 0);
+  if (ny == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_tg_gather, dim3((U + kTrThreads - 1) / kTrThreads, ny), dim3(kTrThreads), 0, s, sigT, cut, U, Up,
+                     M, ncut, Ka, Kz, tab, sizes, (unsigned long long*)all, (unsigned long long*)same);
+  return hipGetLastError();
+}
+
+hipError_t launch_tg_expand(const uint32_t* group_of, const int32_t* cut, int N, int32_t* cl, hipStream_t s) {
+  hipLaunchKernelGGL(k_tg_expand, dim3((N + kTrThreads - 1) / kTrThreads), dim3(kTrThreads), 0, s, group_of, cut, N,
+                     cl);
+  return hipGetLastError();
+}
+
 }  // namespace hdpm

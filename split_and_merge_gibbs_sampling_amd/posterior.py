@@ -13,7 +13,9 @@ The N x N matrix is built and queried on the device (csrc/posterior.hip through
 ``hdpm_psm_*``): at C4 (N = 70k) it has 4.9e9 entries.  ``LabelTrace`` gives the same
 summaries of candidate partitions (VI.lb, the expected VI, Binder's loss) from the saved
 labels alone (csrc/trace_summary.hip through ``hdpm_trace_*``), for sizes where the matrix
-cannot be held (C5: N = 1M would be 4 TB).  ``arandi``, ``ess`` and ``iat`` are
+cannot be held (C5: N = 1M would be 4 TB), and ``minvi_avg`` / ``minbinder_avg`` run minVI's
+default search -- the cuts of the average-linkage tree -- on the groups of points whose
+labels agree in every draw, again with no matrix.  ``arandi``, ``ess`` and ``iat`` are
 restated on the host.  None of these packages is installed here (no R), so their parity is
 unpinned; ``arandi`` is checked against scikit-learn's adjusted Rand score.
 """
@@ -190,6 +192,95 @@ class LabelTrace:
         return out
 
 
+    # ---- the average-linkage tree without the matrix (hdpm_trace_groups .. _cut_labels)
+
+    def groups(self, max_groups: int = 8192, hash_bits: int = 0) -> dict:
+        """The groups of points whose labels agree in every draw, numbered by ascending
+        smallest member: {"U", "first" (U), "weight" (U), "group_of" (N), "counts" (U x U
+        uint32: the draws in which two groups share a cluster)}.  More than ``max_groups``
+        distinct label columns (at most 16384) raise ``HdpmError``: such a trace is too
+        unsettled for the tree.  ``hash_bits`` (1..32) truncates the device's hash (testing);
+        it changes no result."""
+        U = C.c_int32(0)
+        self.eng._check(self.eng._L.hdpm_trace_groups(self.eng._h, int(max_groups), int(hash_bits), C.byref(U)))
+        self.U = U = int(U.value)
+        first, weight = np.zeros(U, np.int32), np.zeros(U, np.int32)
+        group_of, counts = np.zeros(self.N, np.int32), np.zeros((U, U), np.uint32)
+        self.eng._check(self.eng._L.hdpm_trace_group_info(self.eng._h, ptr(first), ptr(weight), ptr(group_of),
+                                                          ptr(counts)))
+        return {"U": U, "first": first, "weight": weight, "group_of": group_of, "counts": counts}
+
+    def avg_tree(self):
+        """(merge, height) of weighted average linkage on the groups (``groups`` first):
+        hclust(as.dist(1 - psm), "average") above height 0.  merge is (U - 1) x 2, each
+        cluster named by its lowest-numbered group, column 0 the name the merged cluster
+        keeps; ties are broken as include/hdpm.h states, in exact integer arithmetic.
+        height = 1 - the average psm between the two clusters (inspection only)."""
+        U = getattr(self, "U", 1)
+        merge, height = np.zeros((max(U - 1, 0), 2), np.int32), np.zeros(max(U - 1, 0))
+        self.eng._check(self.eng._L.hdpm_trace_avg_tree(self.eng._h, ptr(merge), ptr(height)))
+        return merge, height
+
+    def cut(self, k: int) -> np.ndarray:
+        """cutree(k): the tree's partition into k clusters (1..U), labels 0..k-1 in order of
+        first appearance (``avg_tree`` first)."""
+        cl = np.zeros(self.N, np.int32)
+        self.eng._check(self.eng._L.hdpm_trace_cut_labels(self.eng._h, int(k), ptr(cl)))
+        return cl
+
+    def cut_losses(self, k0: int, nk: int):
+        """(vi_lb, vi, binder_A, binder_Q) of the cuts k0 .. k0 + nk - 1 (at most min(U, 255)),
+        from tables over the groups: the values ``vi_lb`` / ``vi`` / ``binder_terms`` give for
+        ``cut(k)``."""
+        lb, v = np.zeros(nk), np.zeros(nk)
+        a, q = np.zeros(nk, np.uint64), np.zeros(nk, np.uint64)
+        self.eng._check(self.eng._L.hdpm_trace_cut_losses(self.eng._h, int(k0), int(nk), ptr(lb), ptr(v), ptr(a),
+                                                          ptr(q)))
+        return lb, v, a, q
+
+
+def _avg_cuts(trace, max_k, max_groups):
+    if not isinstance(trace, LabelTrace):
+        raise ValueError("the matrix-free average-linkage search needs a LabelTrace")
+    U = trace.groups(max_groups)["U"] if max_groups is not None else trace.groups()["U"]
+    trace.avg_tree()
+    kmax = max_k if max_k is not None else math.ceil(trace.N / 8)
+    if kmax < 1:
+        raise ValueError("max_k must be at least 1")
+    # cuts into more than U clusters split groups of identical points and never win; the
+    # trace tables hold at most 255 clusters
+    return min(int(kmax), U, 255)
+
+
+def minvi_avg(trace: LabelTrace, max_k: int | None = None, loss: str = "VI.lb", max_groups: int | None = None):
+    """mcclust.ext::minVI(method = "avg") from a ``LabelTrace``, with no N x N matrix: the
+    cuts k = 1..max_k (default ceiling(N / 8); at most min(U, 255)) of the average-linkage
+    tree of 1 - psm, built on the U groups of identical label columns.  ``loss`` as in
+    ``minvi``.  Returns (cl, value) with cl 1-based."""
+    if loss not in ("VI.lb", "VI"):
+        raise ValueError(f"unknown loss {loss!r}")
+    kmax = _avg_cuts(trace, max_k, max_groups)
+    lb, v, _, _ = trace.cut_losses(1, kmax)
+    vals = v if loss == "VI" else lb
+    best = int(np.argmin(vals))
+    return trace.cut(best + 1) + 1, float(vals[best])
+
+
+def minbinder_avg(trace: LabelTrace, max_k: int | None = None, max_groups: int | None = None):
+    """mcclust::minbinder(method = "avgl") from a ``LabelTrace``: the cut of the same tree
+    minimising Binder's loss, the argmin taken on the exact integers M A + P - 2 Q.  Returns
+    (cl, value) with cl 1-based and the value of ``LabelTrace.binder``."""
+    kmax = _avg_cuts(trace, max_k, max_groups)
+    _, _, A, Q = trace.cut_losses(1, kmax)
+    c, p = np.zeros((1, trace.N), np.int32), np.zeros(1, np.uint64)      # P alone: no table pass
+    trace.eng._check(trace.eng._L.hdpm_trace_losses(trace.eng._h, ptr(c), 1, None, None, None, ptr(p)))
+    P = int(p[0])
+    A, Q = [int(x) for x in A], [int(x) for x in Q]
+    num = [trace.M * a + P - 2 * q for a, q in zip(A, Q)]
+    best = min(range(len(num)), key=num.__getitem__)
+    return trace.cut(best + 1) + 1, float(A[best] + (P - 2 * Q[best]) / trace.M)
+
+
 def comp_psm(c_trace, device: int = 0) -> np.ndarray:
     """mcclust::comp.psm: the full N x N matrix (moderate N)."""
     p = PSM(c_trace, device=device)
@@ -205,7 +296,7 @@ def minvi(psm, cls_draw=None, method: str = "avg", max_k: int | None = None, los
     matrix) and "draws" (the saved partitions).  Returns (cl, value) with cl 1-based.
 
     ``psm`` is a ``PSM`` or, for "draws", a ``LabelTrace`` (no matrix: "avg" raises
-    ValueError).  ``loss`` is "VI.lb" (the lower bound minVI minimises) or "VI" (the
+    ValueError; ``minvi_avg`` is the same search from a ``LabelTrace``).  ``loss`` is "VI.lb" (the lower bound minVI minimises) or "VI" (the
     posterior expected VI itself, mcclust.ext VI(cls, cls.draw); needs a ``LabelTrace``)."""
     if loss not in ("VI.lb", "VI"):
         raise ValueError(f"unknown loss {loss!r}")

@@ -12,6 +12,20 @@ One JSON line per run:
   c5  N = 1,000,000, M = 64 draws of the same 90%-truth shape, 64 candidates: the
       matrix-free path only (the dense one would need 4 TB).
 "device_bytes" is the drop in free device memory while the summary object is alive.
+
+    python tools/trace_summary_bench.py --avg [--dense-n n]
+    python tools/trace_summary_bench.py --run avg-c4 | avg-c5 | avg-synth
+
+--avg: minVI(method = "avg") without the matrix (LabelTrace.groups / avg_tree / cut_losses,
+minvi_avg) on traces recorded from the bench's own chains (truth init, Neal-8, m = 3, 20
+iterations of warm-up, then M consecutive saved iterations): avg-c4 (N = 70,000, M = 24) and
+avg-c5 (N = 1,000,000, M = 64); avg-synth is a synthetic settled trace (N = 200,000,
+M = 1,000, 8,000 single moved labels) that puts U near the default limit.  One JSON line per run with U (the distinct label columns)
+and the times of grouping, counts (S, with its download), tree (host) and cut losses, and
+minvi_avg end to end on a fresh trace.  The dense path (PSM + scipy's linkage on the N x N
+matrix) is timed beside it on --dense-n evenly spaced points of the same trace (default 4,000;
+0 = skip; the full C4 matrix would be 39 GB of doubles on the host and a 70k-point
+linkage), with the two partitions compared.
 """
 import argparse
 import json
@@ -24,6 +38,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 RUNS = {"c4": 600, "c5": 420}       # seconds allowed per run
+AVG_RUNS = {"avg-c4": 420, "avg-c5": 420, "avg-synth": 420}
 
 
 def labels(N, M, seed):
@@ -87,17 +102,124 @@ def run(name):
     print(json.dumps(res), flush=True)
 
 
+def chain_trace(cfg, M, warmup=20):
+    """M consecutive saved iterations of the bench's chain on config cfg"""
+    import numpy as np
+    import split_and_merge_gibbs_sampling_amd as hd
+    from split_and_merge_gibbs_sampling_amd.data import config
+    ds = config(cfg)
+    eng = hd.Engine(0)
+    eng.set_data(ds.codes, ds.attrisize, ds.gamma, ds.v, ds.w)
+    eng.set_seed(1)
+    params = eng.chain_params(m=3, iterations=warmup + M, L=0, burnin=0, neal8=True, split_merge=False, t=10, r=10)
+    eng.init_chain(params, c_i=ds.truth)
+    eng.iterations(0, warmup)
+    tr = np.array(eng.iterations_record(warmup, M)[3])
+    eng.close()
+    assert tr.shape == (M, ds.n), tr.shape
+    return tr
+
+
+def same_partition(a, b):
+    import numpy as np
+
+    def canon(c):
+        _, idx, inv = np.unique(c, return_index=True, return_inverse=True)
+        rank = np.empty(idx.size, np.int64)
+        rank[np.argsort(idx)] = np.arange(idx.size)
+        return rank[inv.ravel()]
+    return bool(np.array_equal(canon(a), canon(b)))
+
+
+def run_avg(name, dense_n):
+    import numpy as np
+    from split_and_merge_gibbs_sampling_amd import HdpmError
+    from split_and_merge_gibbs_sampling_amd.posterior import PSM, LabelTrace, minvi, minvi_avg
+    free_bytes()                                 # torch's device context first, as in run()
+    if name == "avg-synth":
+        # a settled base partition with 8,000 single moved labels: every moved point is a
+        # column of its own, so U is near the default limit and M = 1,000 is the issue's size
+        N, M = 200_000, 1000
+        rng = np.random.default_rng(9)
+        base = rng.integers(0, 10, N).astype(np.int32)
+        tr = np.tile(base, (M, 1))
+        pts = rng.choice(N, 8000, replace=False)
+        tr[rng.integers(0, M, pts.size), pts] = rng.integers(0, 10, pts.size)
+    else:
+        cfg, M = ("c4", 24) if name == "avg-c4" else ("c5", 64)
+        tr = chain_trace(cfg, M)
+    N = tr.shape[1]
+    res = {"run": name, "N": N, "M": M,
+           "moved_per_draw": round(float(np.mean(tr[1:] != tr[:-1]) * N), 1)}
+    f0 = free_bytes()
+    t = LabelTrace(tr)
+    try:
+        t0 = time.perf_counter()
+        U = C_groups(t)
+        t1 = time.perf_counter()
+        counts = np.zeros((U, U), np.uint32)
+        t.eng._check(t.eng._L.hdpm_trace_group_info(t.eng._h, None, None, None, counts.ctypes.data))
+        t2 = time.perf_counter()
+        t.avg_tree()
+        t3 = time.perf_counter()
+        kmax = min(U, 255, -(-N // 8))
+        lb = t.cut_losses(1, kmax)[0]
+        t4 = time.perf_counter()
+        res.update(U=U, groups_s=round(t1 - t0, 4), counts_s=round(t2 - t1, 4), tree_s=round(t3 - t2, 4),
+                   cut_losses_s=round(t4 - t3, 4), cuts=kmax, best_k=int(np.argmin(lb)) + 1,
+                   vi_lb=float(lb.min()), device_bytes=int(f0 - free_bytes()))
+    except HdpmError as e:
+        res["refused"] = str(e)
+    t.close()
+    if "refused" not in res:
+        t0 = time.perf_counter()
+        t = LabelTrace(tr)
+        cl, v = minvi_avg(t)
+        res["minvi_avg_total_s"] = round(time.perf_counter() - t0, 4)
+        t.close()
+        assert v == res["vi_lb"]
+    if dense_n and "refused" not in res:
+        sub = np.ascontiguousarray(tr[:, ::max(1, N // dense_n)][:, :dense_n])      # every cluster present
+        t0 = time.perf_counter()
+        t = LabelTrace(sub)
+        cl_t, v_t = minvi_avg(t)
+        t1 = time.perf_counter()
+        t.close()
+        p = PSM(sub)
+        cl_p, v_p = minvi(p, method="avg")
+        t2 = time.perf_counter()
+        p.close()
+        res["dense_n"] = {"n": int(sub.shape[1]), "U": int(t.U), "trace_s": round(t1 - t0, 4),
+                          "dense_s": round(t2 - t1, 4), "same_partition": same_partition(cl_t, cl_p),
+                          "vi_lb_rel_diff": abs(v_t - v_p) / abs(v_p) if v_p else abs(v_t - v_p)}
+    print(json.dumps(res), flush=True)
+
+
+def C_groups(t):
+    import ctypes
+    U = ctypes.c_int32(0)
+    t.eng._check(t.eng._L.hdpm_trace_groups(t.eng._h, 16384, 0, ctypes.byref(U)))
+    t.U = int(U.value)
+    return t.U
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--run", choices=sorted(RUNS))
+    ap.add_argument("--run", choices=sorted(RUNS) + sorted(AVG_RUNS))
+    ap.add_argument("--avg", action="store_true", help="the matrix-free average-linkage search on recorded chains")
+    ap.add_argument("--dense-n", type=int, default=4000, help="--avg: points of the dense comparison (0: none)")
     a = ap.parse_args()
+    if a.run in AVG_RUNS:
+        run_avg(a.run, a.dense_n)
+        return 0
     if a.run:
         run(a.run)
         return 0
     # the parent never opens the GPU; a run that fails or overruns ends the tool
-    for name, limit in RUNS.items():
+    for name, limit in (AVG_RUNS if a.avg else RUNS).items():
+        extra = ["--dense-n", str(a.dense_n)] if a.avg else []
         st = subprocess.run(["timeout", "-k", "10", str(limit), sys.executable, "-u", os.path.abspath(__file__),
-                             "--run", name]).returncode
+                             "--run", name] + extra).returncode
         if st != 0:
             print(json.dumps({"run": name, "failed": st}), flush=True)
             return st
