@@ -69,7 +69,9 @@ typedef struct {
     double  t_sm_ms, t_sm_scan_ms, t_sm_phi_ms, t_sm_terms_ms;
     /* update_phi on the device (csrc/phi.hip): updates committed there, and updates it
      * handed back to the host (a case it does not restate: Walker, rhig's bisection path, a
-     * drift outside its window, ...); the status of the last one (PhiStatus, 0 = ok) */
+     * drift outside its window, ...); the status of the last one (PhiStatus, 0 = ok).  One
+     * update_phi counts once: a speculated update that did not complete and was run again
+     * counts as what the second run did (its status stays in phi_fallback_status_mask) */
     int64_t phi_device_calls, phi_device_fallbacks, phi_device_last_status;
     /* update stream slices found in a copy made an iteration ahead, and such copies made */
     int64_t phi_lookahead_hits, phi_lookahead_copies;
@@ -337,6 +339,13 @@ int hdpm_get_pool_heads(hdpm_ctx* ctx, uint64_t* out, int64_t P);
  * 2 + 3k turns the chain off at scan k (the host continues from there), 3 + 3k / 4 + 3k hand the
  * scan's update of the lower / larger label back.  Same chain either way (hdpm_stats.sm_chain_*). */
 #define HDPM_OPT_SM_CHAIN 9
+/* HDPM_OPT_PHI_SD_SCALE (testing, default 1): a factor in [0, 1] on the standard-deviation term of
+ * the device update_phi's drift windows (csrc/kernels.hpp phi_lo / phi_hi), on the fast path, the
+ * composition trees and the walks, split-merge's updates and their wider re-runs included.  Below 1
+ * the drift leaves the windows at ordinary sizes, so an update ends with a window status and goes
+ * to the host (or, in split-merge, is re-run with a wider window).  Values outside [0, 1] are an
+ * argument error.  Same chain either way. */
+#define HDPM_OPT_PHI_SD_SCALE 11
 int hdpm_set_option(hdpm_ctx* ctx, int32_t option, double value);
 /* The current value of an option (the same units as hdpm_set_option; HDPM_OPT_PHI_DEVICE
  * reads 1 when update_phi runs on the device, which may be the default). */

@@ -43,6 +43,7 @@ OPT_LAT_NEGLIGIBLE = 7
 OPT_SM_WIDE_WAIT_US = 8
 OPT_SM_CHAIN = 9
 OPT_CAPTURE_DELAY_US = 10
+OPT_PHI_SD_SCALE = 11
 
 STATUS = {0: "OK", 1: "E_VALIDATE", 2: "E_GSL", 3: "E_PROB", 4: "E_WALKER", 5: "E_ARG",
           6: "E_DEVICE", 7: "E_NODEVICE"}

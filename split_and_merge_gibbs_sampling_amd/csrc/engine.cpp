@@ -4011,12 +4011,15 @@ struct Ctx {
   };
   // sd_scale < 1 narrows the drift windows (the fast path: kPhiFastSd standard deviations
   // instead of kPhiSd; a drift outside them is a window status and the update goes to the host)
+  // (phi_sd_scale: HDPM_OPT_PHI_SD_SCALE, testing; 1 by default, and x * 1.0 is x exactly)
+  double phi_sd_scale = 1.0;
   PhiPlan phi_plan(int T, bool sm = false, double sd_scale = 1.0) const {
     PhiPlan pl;
     if (T <= 0 || d > 2048) return pl;
     pl.T = T;
     const double p = sm ? phd.p_rej_sm : phd.p_rej;
     pl.rate = 2 * p / (1 - p);
+    sd_scale *= phi_sd_scale;
     pl.sdev = sd_scale * 2 * std::sqrt(p) / (1 - p);
     pl.items = (int64_t)T * d;
     const int64_t klast = pl.items - 1;
@@ -4869,6 +4872,7 @@ struct Ctx {
     const bool use_dspec = nidx == 0 && dspec.ran && dspec.lv == labels_version && dspec.moves == 0 &&
                            dspec.pos == rng.pos && dspec.epoch == rng.epoch && K == dspec.K && dspec_on();
     if (pre.active && !(use_spec && spec.moves == 0 && K == spec.K && spec.nvalid == K) && !use_dspec) pre_release();
+    const int64_t spec_fallbacks = stats.phi_device_fallbacks;
     if (use_dspec) {
       mark("dspec_wait");
       if (dspec_commit() == kOk) {
@@ -4881,7 +4885,15 @@ struct Ctx {
     dspec.ran = false;
     if (!use_spec) {
       // the update on the device (csrc/phi.hip); -1: not applicable here, the host runs it
+      const bool spec_counted = stats.phi_device_fallbacks > spec_fallbacks;
+      const int64_t counted = stats.phi_device_calls + stats.phi_device_fallbacks;
       const int st = device_update_phi(mask, nidx);
+      // one update, one count: a speculation that did not complete (dspec_commit counted a
+      // hand-back, its status stays in the mask) gives way to the outcome of this re-run
+      if (spec_counted && stats.phi_device_calls + stats.phi_device_fallbacks > counted) {
+        phd.fallbacks--;
+        stats.phi_device_fallbacks--;
+      }
       if (st >= 0) return st;
     }
     int t0 = 0;
@@ -5678,6 +5690,7 @@ int hdpm_get_option(hdpm_ctx* h, int32_t option, double* value) {
     case HDPM_OPT_SM_WIDE_WAIT_US: *value = (double)ctx->sm_wide_ticks * 0.01; return HDPM_OK;
     case HDPM_OPT_SM_CHAIN: *value = (double)ctx->sm_chain_mode; return HDPM_OK;
     case HDPM_OPT_CAPTURE_DELAY_US: *value = ctx->capture_delay_us; return HDPM_OK;
+    case HDPM_OPT_PHI_SD_SCALE: *value = ctx->phi_sd_scale; return HDPM_OK;
     default:
       ctx->err = "unknown option";
       return HDPM_E_ARG;
@@ -5739,6 +5752,11 @@ int hdpm_set_option(hdpm_ctx* h, int32_t option, double value) {
     case HDPM_OPT_CAPTURE_DELAY_US:
       if (!(value >= 0.0) || !(value <= 1e6)) { ctx->err = "capture delay must be in [0, 1e6] us"; return HDPM_E_ARG; }
       ctx->capture_delay_us = value;
+      return HDPM_OK;
+    case HDPM_OPT_PHI_SD_SCALE:
+      if (!(value >= 0.0) || !(value <= 1.0)) { ctx->err = "phi sd scale must be in [0, 1]"; return HDPM_E_ARG; }
+      GUARD(ctx->cancel_ahead();)
+      ctx->phi_sd_scale = value;
       return HDPM_OK;
     default:
       ctx->err = "unknown option";

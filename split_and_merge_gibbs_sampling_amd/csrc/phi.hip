@@ -531,7 +531,12 @@ __device__ __forceinline__ int64_t phi_walk_cluster(const PhiArgs& a, const PhiC
   }
   wave_lds_sync();
   if (__ballot(bad)) {
-    if (*why == 0) *why = kPhiShort;
+    // the wave's reason (the caller's lane 0 reports it): the largest of the lanes', as
+    // set_status would keep it; none: a center's uniform past the slice
+    int w = *why;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) w = max(w, __shfl_xor(w, o));
+    *why = w ? w : kPhiShort;
     return -1;
   }
   for (int j0 = 0; j0 < d; j0 += 64) {
@@ -543,8 +548,11 @@ __device__ __forceinline__ int64_t phi_walk_cluster(const PhiArgs& a, const PhiC
     int64_t wlo = 0;
     if (act) {
       const int64_t lo = phi_lo(k, a.rate, a.sdev);
-      const int64_t q = delta >= lo ? (delta - lo) >> 6 : -1;
-      if (q < 0 || q >= a.nw) bad = true;
+      // (a later lane's window may start past the batch's start drift -- its own drift is that
+      // plus the extras of the lanes before it: its words are then read from its first one, and
+      // the drift it ends the rounds with is checked against its window below)
+      const int64_t q = delta >= lo ? (delta - lo) >> 6 : 0;
+      if (q >= a.nw) bad = true;
       else {
         if (C.det[j]) {                        // LDS image
           const uint64_t* m = C.maskd + (int64_t)j * a.nw;
@@ -563,12 +571,14 @@ __device__ __forceinline__ int64_t phi_walk_cluster(const PhiArgs& a, const PhiC
     if (__ballot(bad)) { *why = kPhiWindow; return -1; }
     int64_t dl = delta;
     int ex = 0, tot = 0;
+    bool low = false;                          // the lane's drift is still below its window
     for (;;) {
       ex = 0;
       if (act) {
         int o = (int)(dl - wlo);
-        ex = -1;
-        for (int r = 0; o < 192; ++r, o += 2) {
+        low = o < 0;
+        ex = low ? 0 : -1;
+        for (int r = 0; !low && o < 192; ++r, o += 2) {
           const uint64_t wd = o < 64 ? w0 : o < 128 ? w1 : w2;
           if ((wd >> (o & 63)) & 1ull) { ex = 2 * r; break; }
         }
@@ -581,6 +591,7 @@ __device__ __forceinline__ int64_t phi_walk_cluster(const PhiArgs& a, const PhiC
       dl = nd;
       if (!__ballot(changed)) break;
     }
+    if (__ballot(act && low)) { *why = kPhiWindow; return -1; }
     if (act && sapos) sapos[j] = base + d + 2 * (int64_t)j + dl + ex;   // the accepted attempt
     delta += tot;
   }
@@ -743,6 +754,33 @@ __global__ __launch_bounds__(1024) void k_phi_cwalk(PhiArgs a) {
   }
 }
 
+// Why cluster t cannot be walked from its start drift dt whatever its windows (one thread, on the
+// hand-back path only): a pick -- the fixed one, or the one the center's uniform at dt takes --
+// whose sigma the device does not draw (kPhiBisect, kPhiInactive), or a center uniform past the
+// slice (kPhiShort); the largest, as set_status keeps it; 0: every pick is drawn here.
+__device__ int phi_cluster_why(const PhiArgs& a, int t, int64_t dt) {
+  const int d = a.d;
+  const int64_t base = (int64_t)t * 3 * d;
+  int why = 0;
+  for (int j = 0; j < d; ++j) {
+    int kd;
+    if (a.det[(int64_t)t * d + j]) {
+      kd = a.ikind[(int64_t)t * d + j];
+    } else {
+      const int64_t pos = base + dt + j;
+      if (pos >= a.span) { why = max(why, (int)kPhiShort); continue; }
+      const double rU = pool_unif(a.raw[pos]);
+      const int64_t cb = (int64_t)t * a.sumatt + a.aoff[j];
+      int s;
+      for (s = 0; s < a.att[j] - 1; ++s)
+        if (rU <= a.cum[cb + s]) break;
+      kd = a.cand[cb + a.perm[cb + s] - 1].kind;
+    }
+    if (kd != 2 && kd != 3) why = max(why, kd == 1 ? (int)kPhiBisect : (int)kPhiInactive);
+  }
+  return why;
+}
+
 // One walk segment of cluster t from drift `delta` by one thread, from global memory (a
 // segment after the first whose picks depend on the uniform, i.e. on the cluster's start
 // drift dt, which its table cannot index): the end drift, or < 0.
@@ -817,7 +855,12 @@ __global__ __launch_bounds__(1024) void k_phi_chain(PhiArgs a) {
       if (c < 0 || c >= a.Wc) { set_status(a.status, kPhiWindow); return; }
       int64_t e = F[((int64_t)t * a.S + sg) * a.Wc + c];
       if (e == -2 && sg > 0) e = phi_walk_serial(a, t, sg * a.L, min(a.d, (sg + 1) * a.L), a.dts[t], delta);
-      if (e < 0) { set_status(a.status, kPhiWindow); return; }
+      if (e < 0) {
+        // -2 / -3: a pick the device does not draw (or its uniform past the slice), not the windows
+        const int why = e == -2 || e == -3 ? phi_cluster_why(a, t, a.dts[t]) : 0;
+        set_status(a.status, why ? why : kPhiWindow);
+        return;
+      }
       delta = e;
     }
   }
@@ -1190,22 +1233,27 @@ __global__ __launch_bounds__(1024) void k_phi_values2(PhiArgs a) {
   }
   __syncthreads();
   if (threadIdx.x == 0) {
-    int e = 0;
+    int e = 0, why = 0;
     bool ok = true;
     for (int u = 0; u < t && ok; ++u) {
       const int c = e - (int)phi_lo((int64_t)u * d, a.rate, a.sdev);
       if ((unsigned)c >= (unsigned)W) { ok = false; break; }
       const uint16_t v = R[(size_t)u * W + c];
-      if (v == kPhiBad) ok = false;
-      else e += v;
+      if (v == kPhiBad) {
+        // (a walked cluster's entry is also bad where a pick at that start is not drawn here)
+        ok = false;
+        if (a.tnd[u]) why = phi_cluster_why(a, u, e);
+      } else {
+        e += v;
+      }
     }
     sdt = ok ? e : -1;
-    if (!ok) sbad = 1;
+    if (!ok) sbad = why ? why : kPhiWindow;
     else a.dts[t] = e;
   }
   __syncthreads();
   if (sbad) {
-    if (threadIdx.x == 0) set_status(a.status, kPhiWindow);
+    if (threadIdx.x == 0) set_status(a.status, sbad);
     return;
   }
   const uint16_t* G = a.tree + (int64_t)a.tpc * W * t;

@@ -232,6 +232,11 @@ class Engine:
         iterations_record reads a saved iteration's labels from device memory (0: none)."""
         self._check(self._L.hdpm_set_option(self._h, _lib.OPT_CAPTURE_DELAY_US, float(us)))
 
+    def set_phi_sd_scale(self, scale: float):
+        """Testing (include/hdpm.h HDPM_OPT_PHI_SD_SCALE): a factor in [0, 1] on the standard-
+        deviation term of the device update_phi's drift windows; same chain either way."""
+        self._check(self._L.hdpm_set_option(self._h, _lib.OPT_PHI_SD_SCALE, float(scale)))
+
     def set_fpg_wait_us(self, us: float):
         """The grid-barrier limit of the device-wide resolver (include/hdpm.h
         HDPM_OPT_FPG_WAIT_US); a launch that gives up is continued on one workgroup."""

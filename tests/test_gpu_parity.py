@@ -203,11 +203,52 @@ def test_device_update_phi_fast_path_converged(hd, oracle, shape):
 
 
 def test_device_update_phi_small_clusters_fall_back_or_match(hd, oracle, zoo):
-    # all-singleton Zoo clusters: rhig's bisection path and center levels that depend on the
-    # uniform; whatever the device hands back, the chain is the oracle's
+    # all-singleton Zoo clusters: center levels that depend on the uniform, and far more rejected
+    # rbeta attempts than the drift windows expect (no draw takes rhig's bisection branch here);
+    # whatever the device hands back, the chain is the oracle's
+    # (what each update meets is predicted on the CPU from the oracle's states, tests/phi_predict.py:
+    # an update with a Walker item or a drawn center on rhig's bisection branch is handed back,
+    # any other is committed unless its drift may have left the windows; under Zoo's priors no
+    # cluster below 9 members reaches the bisection branch)
+    import phi_predict as PP
     c = np.arange(zoo.n, dtype=np.int32)
     cen, sig = random_params(zoo, zoo.n, 5)
-    stats = sweep_case(hd, oracle, zoo, c, cen, sig, zoo.n * 3, seed=23, sweeps=3, phi=True, phi_device=True)
+    st = oracle.seed_state(23)
+    pc, ps, s0 = oracle.pool_generate(zoo.attrisize, zoo.v, zoo.w, zoo.n * 3, st)
+    assert s0 == 0
+    eng = make_engine(hd, zoo)
+    eng.set_phi_device(True)
+    eng.set_state(c, cen, sig)
+    eng.set_pool(pc, ps)
+    eng.rng_state = st
+    ost = oracle_state(oracle, c, cen, sig)
+    rng = st.copy()
+    allowed = 0
+    for it in range(3):
+        eng.neal8_sweep(3)
+        assert oracle.neal8_sweep(zoo.codes, zoo.attrisize, zoo.gamma, zoo.v, zoo.w, ost, 3, pc, ps, rng, fast=1) == 0
+        assert_same_state(eng, ost)
+        assert np.array_equal(eng.rng_state, rng)
+        before, sig_before, rng_before = eng.stats(), ost.sigma[:ost.K].copy(), rng.copy()
+        eng.update_phi()
+        assert oracle.update_phi(zoo.codes, zoo.attrisize, zoo.v, zoo.w, ost, rng) == 0
+        assert_same_state(eng, ost)
+        assert np.array_equal(eng.rng_state, rng)
+        consumed = PP.stream_distance(oracle, rng_before, rng, 40 * ost.K * zoo.d + 1000)
+        p = PP.UpdatePrediction(oracle, zoo, ost.c_i, ost.K, sig_before, ost.centers[:ost.K], consumed)
+        after = eng.stats()
+        committed = after["phi_device_calls"] - before["phi_device_calls"]
+        handed = after["phi_device_fallbacks"] - before["phi_device_fallbacks"]
+        assert committed + handed == 1, (it, committed, handed)
+        if p.handed_back:
+            assert committed == 0, it
+        elif not (p.may_leave_window or p.ambiguous):
+            assert committed == 1, (it, p.z)
+        if handed:
+            allowed |= p.allowed_mask()
+        assert after["phi_fallback_status_mask"] & ~allowed == 0, (it, after["phi_fallback_status_mask"], allowed)
+    stats = eng.stats()
+    eng.close()
     assert stats["phi_device_calls"] + stats["phi_device_fallbacks"] == 3
 
 

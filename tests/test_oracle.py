@@ -64,6 +64,23 @@ def test_qbeta_branch_against_scipy(oracle):
         assert oracle.lib().orc_ffi_qbeta01_lt(a, b, x) == int(q < x)
 
 
+def test_norm_const2_throws_from_200_levels(oracle):
+    """The split-merge prior's constant norm_const2(w, v, m) (sm:419-436) at the usual priors:
+    defined up to 100 levels, the reference throws at 200 and 255 (GSL's 2F1 at z = (m - 1) / m),
+    with and without the log-space extension -- so a split-merge move is undefined on such an
+    attribute (tests/test_gpu_phi_edges.py keeps its split-merge data at 64 levels)."""
+    for logspace in (False, True):
+        oracle.set_hig_logspace(logspace)
+        try:
+            for m in (2.0, 17.0, 64.0, 100.0):
+                v, err = oracle.norm_const2(0.25, 6.0, m)
+                assert err == 0 and np.isfinite(v), (logspace, m)
+            for m in (200.0, 255.0):
+                assert oracle.norm_const2(0.25, 6.0, m)[1] == 2, (logspace, m)
+        finally:
+            oracle.set_hig_logspace(False)
+
+
 def test_norm_const2_against_mpmath(oracle):
     mp = pytest.importorskip("mpmath")
     for d, c, m in [(0.25, 6.0, 2.0), (3.5, 40.0, 4.0), (10.25, 200.0, 6.0)]:
