@@ -389,6 +389,29 @@ int hdpm_trace_terms(hdpm_ctx* ctx, const int32_t* cls, int32_t ncand, uint64_t*
 int hdpm_trace_losses(hdpm_ctx* ctx, const int32_t* cls, int32_t ncand, double* vi_lb, double* vi,
                       uint64_t* binder_Q, uint64_t* binder_P);
 int hdpm_trace_tables(hdpm_ctx* ctx, const int32_t* cls, int32_t ncand, int32_t m0, int32_t nm, uint32_t* out);
+/* How far an estimate can be trusted (mcclust.ext credibleball and the block structure of the
+ * PSM ordered by the estimate's classes), after hdpm_trace_build and with its refusals.
+ *
+ * hdpm_trace_distances: the distance of every candidate cls[ncand x N] to every saved draw.
+ *   vi[c * M + m] = (sum_a n_a log2 n_a + sum_b n^m_b log2 n^m_b - 2 sum_ab T^m log2 T^m) / N,
+ *   the variation of information, evaluated as (hc + S_m - 2 l) / N in that order with hc as
+ *   in hdpm_trace_losses, so draws with equal labels give bit-equal values; a result that
+ *   rounding took below 0 is returned as 0.0.  binder[c * M + m] = A_c + P_m - 2 Q_cm, the
+ *   number of pairs i < j on which the two partitions disagree (A_c = sum_a C2(n_a), P_m =
+ *   sum_b C2(n^m_b), Q_cm = sum_ab C2(T^m[a][b])): the exact pair count, not mcclust's
+ *   scaling of Binder's loss, which is unpinned here.  draw_k[m] = the clusters of draw m.
+ *   Any output may be NULL; draw_k alone runs no table pass.
+ * hdpm_trace_affinity: one partition cl[N] with labels 0..Ka-1, 1 <= Ka <= 255 (Ka may exceed
+ *   the largest label + 1: empty clusters give zero columns and rows; a label >= Ka is
+ *   HDPM_E_ARG).  aff[i * Ka + a] = sum_m T^m[a][z_m(i)] = M sum_{j: c_j = a} psm_ij (N x Ka)
+ *   and cross[a * Ka + b] = sum_m sum_z T^m[a][z] T^m[b][z] = M sum_{i in a, j in b} psm_ij
+ *   (Ka x Ka, symmetric), exact integers.  Either output may be NULL.  cross needs
+ *   N^2 M < 2^63 (HDPM_E_ARG otherwise).  aff is produced in blocks of points whose device
+ *   staging stays within table_budget_bytes (at least 16 points per block), each copied to
+ *   the caller as it completes; no result depends on the budget. */
+int hdpm_trace_distances(hdpm_ctx* ctx, const int32_t* cls, int32_t ncand, double* vi, uint64_t* binder,
+                         int32_t* draw_k);
+int hdpm_trace_affinity(hdpm_ctx* ctx, const int32_t* cl, int32_t Ka, uint64_t* aff, uint64_t* cross);
 /* mcclust.ext minVI(method = "avg") / mcclust minbinder(method = "avgl") =
  * hclust(as.dist(1 - psm), "average") + cutree, from the saved labels alone.  Points whose
  * labels agree in every draw have psm = 1 (distance 0) and any other pair has distance

@@ -5,7 +5,7 @@ kernels and the host runtime live in ``libhdpm.so`` (C ABI: include/hdpm.h); thi
 package is the Python mirror of the reference interface.
 """
 from ._lib import HdpmError, build  # noqa: F401
-from .posterior import LabelTrace, minbinder  # noqa: F401
+from .posterior import LabelTrace, credible_ball, minbinder  # noqa: F401
 from .sampler import Engine, run_markov_chain  # noqa: F401
 
-__all__ = ["Engine", "run_markov_chain", "HdpmError", "build", "LabelTrace", "minbinder"]
+__all__ = ["Engine", "run_markov_chain", "HdpmError", "build", "LabelTrace", "minbinder", "credible_ball"]

@@ -30,7 +30,7 @@ EXPORTS = (
     "hdpm_psm_build", "hdpm_psm_rows", "hdpm_psm_vi_lb",
     "hdpm_trace_build", "hdpm_trace_terms", "hdpm_trace_losses", "hdpm_trace_tables",
     "hdpm_trace_groups", "hdpm_trace_group_info", "hdpm_trace_avg_tree", "hdpm_trace_cut_losses",
-    "hdpm_trace_cut_labels",
+    "hdpm_trace_cut_labels", "hdpm_trace_distances", "hdpm_trace_affinity",
 )
 
 OPT_HIG_LOGSPACE = 1
@@ -162,6 +162,8 @@ def lib():
         "hdpm_trace_avg_tree": ([vp, vp, vp], C.c_int),
         "hdpm_trace_cut_losses": ([vp, i32, i32, vp, vp, vp, vp], C.c_int),
         "hdpm_trace_cut_labels": ([vp, i32, vp], C.c_int),
+        "hdpm_trace_distances": ([vp, vp, i32, vp, vp, vp], C.c_int),
+        "hdpm_trace_affinity": ([vp, vp, i32, vp, vp], C.c_int),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name)

@@ -85,6 +85,10 @@ hipError_t launch_tr_gather(const uint8_t* lab, const uint8_t* cls, int N, int N
                             hipStream_t s);
 hipError_t launch_tr_reduce(const uint32_t* tab, int ncand, int M, int cells, uint64_t* q1, double* l1, uint64_t* q,
                             double* l, hipStream_t s);
+hipError_t launch_tr_transpose(const uint32_t* tab, int M, int Ka, int Kz, uint32_t* tabT, hipStream_t s);
+hipError_t launch_tr_affinity(const uint8_t* lab, int Np, int M, int Ka, int Kz, const uint32_t* tabT, int i0, int npts,
+                              uint64_t* out, hipStream_t s);
+hipError_t launch_tr_cross(const uint32_t* tabT, int M, int Ka, int Kz, uint64_t* cross, hipStream_t s);
 hipError_t launch_tg_insert(const uint8_t* lab, int N, int Np, int M, int hash_bits, uint32_t tslots,
                             uint32_t max_groups, uint32_t* rep, uint32_t* first, uint32_t* pslot, uint32_t* ctl,
                             hipStream_t s);
@@ -784,6 +788,13 @@ struct Ctx {
   size_t tr_budget = 0;
   uint64_t tr_P = 0;     // sum_m sum_b C2(n^m_b)
   double tr_S = 0.0;     // sum_m sum_b n^m_b log2 n^m_b
+  // per draw (hdpm_trace_distances): P_m, S_m and the cluster count; the estimate's tables
+  // transposed, the staging of one block of points of aff, and cross (hdpm_trace_affinity)
+  std::vector<uint64_t> tr_Pm;
+  std::vector<double> tr_Sm;
+  std::vector<int32_t> tr_Km;
+  DevBuf<uint32_t> d_tr_tabT;
+  DevBuf<uint64_t> d_tr_aff, d_tr_cross;
   // groups of equal label columns and their average-linkage tree (hdpm_trace_groups ..
   // hdpm_trace_cut_labels): the open-addressing table, group_of per point, the groups'
   // signatures both ways round, S (U x U) once it is first needed, the tree on the host
@@ -5868,7 +5879,18 @@ int hdpm_trace_build(hdpm_ctx* h, const int32_t* c_trace, int32_t M, int32_t N, 
                                   ctx->d_tr_l.p, ctx->stream));
     HIPCHK(hipMemcpyAsync(&ctx->tr_P, ctx->d_tr_q.p, 8, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipMemcpyAsync(&ctx->tr_S, ctx->d_tr_l.p, 8, hipMemcpyDeviceToHost, ctx->stream));
+    // the per-draw P_m and S_m stay on the host (later calls reuse d_tr_q1 / d_tr_l1), with
+    // the draws' cluster counts from the size rows
+    ctx->tr_Pm.resize((size_t)M);
+    ctx->tr_Sm.resize((size_t)M);
+    ctx->tr_Km.assign((size_t)M, 0);
+    std::vector<uint32_t> sizes((size_t)M * 256);
+    HIPCHK(hipMemcpyAsync(ctx->tr_Pm.data(), ctx->d_tr_q1.p, (size_t)M * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(ctx->tr_Sm.data(), ctx->d_tr_l1.p, (size_t)M * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(sizes.data(), ctx->d_tr_sizes.p, sizes.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
+    for (int m = 0; m < M; ++m)
+      for (int b = 0; b < 256; ++b) ctx->tr_Km[m] += sizes[(size_t)m * 256 + b] != 0u;
     ctx->tr_M = M;
     ctx->tr_Np = Np;
     ctx->tr_Kz = mx + 1;
@@ -5983,6 +6005,95 @@ int hdpm_trace_tables(hdpm_ctx* h, const int32_t* cls, int32_t ncand, int32_t m0
             std::memcpy(out + (((size_t)(c0 + c) * nm + m) * 256 + a) * 256, t.data() + ((size_t)m * Ka + a) * Kz,
                         (size_t)Kz * 4);
       }
+    });
+    return HDPM_OK;
+  })
+}
+// ---- how far the estimate can be trusted (trace_uncertainty.hip)
+int hdpm_trace_distances(hdpm_ctx* h, const int32_t* cls, int32_t ncand, double* vi, uint64_t* binder,
+                         int32_t* draw_k) {
+  CTX();
+  int Ka = 0;
+  if (int st = trace_check(ctx, cls, ncand, &Ka)) return st;
+  GUARD({
+    const int N = ctx->tr_N, M = ctx->tr_M;
+    if (draw_k) std::memcpy(draw_k, ctx->tr_Km.data(), (size_t)M * 4);
+    if (!vi && !binder) return HDPM_OK;
+    std::vector<uint64_t> q1;
+    std::vector<double> l1, lsz((size_t)Ka);
+    std::vector<int> sz((size_t)Ka);
+    // the per-(candidate, draw) sums of k_tr_reduce, as they stand before k_tr_reduce_draws
+    trace_blocks(ctx, cls, ncand, Ka, false, false, true, [&](int c0, int nc) {
+      q1.resize((size_t)nc * M);
+      l1.resize((size_t)nc * M);
+      HIPCHK(hipMemcpyAsync(q1.data(), ctx->d_tr_q1.p, q1.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+      HIPCHK(hipMemcpyAsync(l1.data(), ctx->d_tr_l1.p, l1.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+      HIPCHK(hipStreamSynchronize(ctx->stream));
+      for (int c = 0; c < nc; ++c) {
+        const int32_t* cl = cls + (size_t)(c0 + c) * N;
+        std::fill(sz.begin(), sz.end(), 0);
+        for (int i = 0; i < N; ++i) sz[cl[i]]++;
+        for (int a = 0; a < Ka; ++a) lsz[a] = sz[a] > 0 ? std::log2((double)sz[a]) : 0.0;
+        // hc as in hdpm_trace_losses; A_c = sum_a C2(n_a)
+        double hc = 0.0;
+        uint64_t A = 0;
+        for (int a = 0; a < Ka; ++a) {
+          hc = hc + (double)sz[a] * lsz[a];
+          A += (uint64_t)sz[a] * (uint64_t)(sz[a] > 0 ? sz[a] - 1 : 0) / 2;
+        }
+        for (int m = 0; m < M; ++m) {
+          const size_t o = (size_t)(c0 + c) * M + m, k = (size_t)c * M + m;
+          if (vi) {
+            const double d = (hc + ctx->tr_Sm[m] - 2 * l1[k]) / N;
+            vi[o] = d < 0.0 ? 0.0 : d;      // rounding can undershoot 0 when c is the draw
+          }
+          if (binder) binder[o] = A + ctx->tr_Pm[m] - 2 * q1[k];
+        }
+      }
+    });
+    return HDPM_OK;
+  })
+}
+int hdpm_trace_affinity(hdpm_ctx* h, const int32_t* cl, int32_t Ka, uint64_t* aff, uint64_t* cross) {
+  CTX();
+  int used = 0;   // the largest label + 1
+  if (int st = trace_check(ctx, cl, 1, &used)) return st;
+  if (Ka < 1 || Ka > 255) { ctx->err = "trace: Ka must be in 1..255"; return HDPM_E_ARG; }
+  if (used > Ka) { ctx->err = "trace: the partition's labels must be in 0..Ka-1"; return HDPM_E_ARG; }
+  const int N = ctx->tr_N, Np = ctx->tr_Np, M = ctx->tr_M, Kz = ctx->tr_Kz;
+  if (cross && ((unsigned __int128)N * (unsigned __int128)N * (unsigned __int128)M >> 63)) {
+    ctx->err = "trace: N^2 M does not fit 63 bits: the sums of cross would overflow";
+    return HDPM_E_ARG;
+  }
+  if (!aff && !cross) return HDPM_OK;
+  GUARD({
+    // one candidate always fits a block of trace_blocks: its tables, then their transpose
+    trace_blocks(ctx, cl, 1, Ka, false, false, false, [&](int, int) {
+      const size_t per = (size_t)M * Ka * Kz;
+      ctx->d_tr_tabT.ensure(per);
+      HIPCHK(hdpm::launch_tr_transpose(ctx->d_tr_tab.p, M, Ka, Kz, ctx->d_tr_tabT.p, ctx->stream));
+      if (cross) {
+        ctx->d_tr_cross.ensure((size_t)Ka * Ka);
+        HIPCHK(hipMemsetAsync(ctx->d_tr_cross.p, 0, (size_t)Ka * Ka * 8, ctx->stream));
+        HIPCHK(hdpm::launch_tr_cross(ctx->d_tr_tabT.p, M, Ka, Kz, ctx->d_tr_cross.p, ctx->stream));
+        HIPCHK(hipMemcpyAsync(cross, ctx->d_tr_cross.p, (size_t)Ka * Ka * 8, hipMemcpyDeviceToHost, ctx->stream));
+      }
+      if (aff) {
+        // blocks of points: the staging (pb x Ka x 8 bytes) within the table budget, in whole
+        // groups of 16 points and at least one; each block goes to the caller as it completes
+        size_t pb = (ctx->tr_budget / ((size_t)Ka * 8)) & ~(size_t)15;
+        pb = std::min(std::max<size_t>(pb, 16), (size_t)Np);
+        ctx->d_tr_aff.ensure(pb * Ka);
+        for (int64_t i0 = 0; i0 < N; i0 += (int64_t)pb) {
+          const int np = (int)std::min<int64_t>((int64_t)pb, N - i0);
+          HIPCHK(hdpm::launch_tr_affinity(ctx->d_tr_lab.p, Np, M, Ka, Kz, ctx->d_tr_tabT.p, (int)i0, np,
+                                          ctx->d_tr_aff.p, ctx->stream));
+          HIPCHK(hipMemcpyAsync(aff + (size_t)i0 * Ka, ctx->d_tr_aff.p, (size_t)np * Ka * 8, hipMemcpyDeviceToHost,
+                                ctx->stream));
+          HIPCHK(hipStreamSynchronize(ctx->stream));
+        }
+      }
+      HIPCHK(hipStreamSynchronize(ctx->stream));
     });
     return HDPM_OK;
   })

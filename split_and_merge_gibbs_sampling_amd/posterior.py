@@ -15,7 +15,10 @@ summaries of candidate partitions (VI.lb, the expected VI, Binder's loss) from t
 labels alone (csrc/trace_summary.hip through ``hdpm_trace_*``), for sizes where the matrix
 cannot be held (C5: N = 1M would be 4 TB), and ``minvi_avg`` / ``minbinder_avg`` run minVI's
 default search -- the cuts of the average-linkage tree -- on the groups of points whose
-labels agree in every draw, again with no matrix.  ``arandi``, ``ess`` and ``iat`` are
+labels agree in every draw, again with no matrix.  ``credible_ball`` (mcclust.ext
+``credibleball``) and ``LabelTrace.membership`` / ``cluster_similarity`` (the content of the
+script's PSM plot ordered by ``VI$cl``) say how far that estimate can be trusted, from the
+same tables (csrc/trace_uncertainty.hip).  ``arandi``, ``ess`` and ``iat`` are
 restated on the host.  None of these packages is installed here (no R), so their parity is
 unpinned; ``arandi`` is checked against scikit-learn's adjusted Rand score.
 """
@@ -191,6 +194,77 @@ class LabelTrace:
         self.eng._check(self.eng._L.hdpm_trace_tables(self.eng._h, ptr(c), c.shape[0], int(m0), nm, ptr(out)))
         return out
 
+    # ---- how far an estimate can be trusted (csrc/trace_uncertainty.hip)
+
+    def distances(self, cls):
+        """(vi, binder, draw_k): the distance of each row of ``cls`` to every saved draw.
+        vi[c][m] is the variation of information (ncand x M doubles; draws with equal labels
+        give bit-equal values), binder[c][m] the number of pairs i < j on which the two
+        partitions disagree (ncand x M uint64, exact: the pair count, not mcclust's scaling of
+        Binder's loss, which is unpinned here), draw_k[m] the number of clusters of draw m."""
+        c = self._cands(cls)
+        vi = np.zeros((c.shape[0], self.M))
+        binder = np.zeros((c.shape[0], self.M), np.uint64)
+        draw_k = np.zeros(self.M, np.int32)
+        self.eng._check(self.eng._L.hdpm_trace_distances(self.eng._h, ptr(c), c.shape[0], ptr(vi), ptr(binder),
+                                                         ptr(draw_k)))
+        return vi, binder, draw_k
+
+    def _one(self, cl) -> np.ndarray:
+        c = self._cands(cl)
+        if c.shape[0] != 1:
+            raise ValueError("one partition of N labels is needed")
+        return c
+
+    def affinity(self, cl):
+        """(aff, cross) of one partition ``cl`` (relabelled 0..Ka-1 as the candidates are):
+        aff[i][a] = sum_m T^m[a][z_m(i)] = M sum_{j: c_j = a} psm_ij (N x Ka) and cross[a][b] =
+        sum_m sum_z T^m[a][z] T^m[b][z] = M sum_{i in a, j in b} psm_ij (Ka x Ka, symmetric),
+        uint64, exact.  aff comes off the device in blocks of points within the table budget."""
+        c = self._one(cl)
+        Ka = int(c.max()) + 1
+        aff = np.zeros((self.N, Ka), np.uint64)
+        cross = np.zeros((Ka, Ka), np.uint64)
+        self.eng._check(self.eng._L.hdpm_trace_affinity(self.eng._h, ptr(c), Ka, ptr(aff), ptr(cross)))
+        return aff, cross
+
+    def membership(self, cl) -> np.ndarray:
+        """N x Ka doubles: the mean psm of point i with the members of cluster a of ``cl``, the
+        point itself excluded, (aff[i][a] - M [c_i = a]) / (M (n_a - [c_i = a])); 1.0 by
+        convention for a point alone in its own cluster.  A row whose arg-max over a differs
+        from c_i marks a point the estimate places against its own average similarity."""
+        c = self._one(cl)[0]
+        Ka = int(c.max()) + 1
+        aff = np.zeros((self.N, Ka), np.uint64)
+        self.eng._check(self.eng._L.hdpm_trace_affinity(self.eng._h, ptr(c), Ka, ptr(aff), None))
+        own = np.zeros((self.N, Ka), np.int64)
+        own[np.arange(self.N), c] = 1
+        num = aff.astype(np.int64) - self.M * own          # aff <= M N < 2^63
+        den = self.M * (np.bincount(c, minlength=Ka).astype(np.int64)[None, :] - own)
+        out = np.ones((self.N, Ka))
+        np.divide(num, den, out=out, where=den > 0)
+        return out
+
+    def cluster_similarity(self, cl) -> np.ndarray:
+        """Ka x Ka doubles: the mean psm between the members of clusters a and b of ``cl``,
+        cross[a][b] / (M n_a n_b); on the diagonal the self pairs are excluded,
+        (cross[a][a] - M n_a) / (M n_a (n_a - 1)), 1.0 for a singleton.  This is the block
+        mean of the PSM ordered by the classes of ``cl``.  The integers are combined as Python
+        ints and divided once."""
+        c = self._one(cl)[0]
+        Ka = int(c.max()) + 1
+        cross = np.zeros((Ka, Ka), np.uint64)
+        self.eng._check(self.eng._L.hdpm_trace_affinity(self.eng._h, ptr(c), Ka, None, ptr(cross)))
+        n = np.bincount(c, minlength=Ka).tolist()
+        x = cross.tolist()
+        out = np.ones((Ka, Ka))
+        for a in range(Ka):
+            for b in range(Ka):
+                if a != b:
+                    out[a, b] = x[a][b] / (self.M * n[a] * n[b])
+                elif n[a] > 1:
+                    out[a, a] = (x[a][a] - self.M * n[a]) / (self.M * n[a] * (n[a] - 1))
+        return out
 
     # ---- the average-linkage tree without the matrix (hdpm_trace_groups .. _cut_labels)
 
@@ -344,6 +418,61 @@ def minbinder(trace: LabelTrace, cls_draw=None, method: str = "draws"):
     best = min(range(len(num)), key=num.__getitem__)
     cl = np.unique(cand[best], return_inverse=True)[1] + 1
     return cl, float(A[best] + (P - 2 * Q[best]) / trace.M)
+
+
+def _ball(d, k, alpha: float) -> dict:
+    """The selection of mcclust.ext::credibleball on the host: ``d`` the M distances of the
+    draws to the estimate (integers or floats), ``k`` their cluster counts.  With r the
+    ceil((1 - alpha) M)-th smallest distance (the index clamped to 1..M), the ball is every
+    draw with d <= r; every tie is kept, in the ball and in each bound.  Returns draw indices
+    (ascending) and the distances of the bounds."""
+    d, k = np.asarray(d), np.asarray(k)
+    if d.ndim != 1 or d.size == 0 or k.shape != d.shape:
+        raise ValueError("d and k must be vectors of the same length M >= 1")
+    if not 0.0 <= alpha <= 1.0:
+        raise ValueError("alpha must lie in [0, 1]")
+    M = d.size
+    idx = min(max(math.ceil((1 - alpha) * M), 1), M)
+    r = np.sort(d)[idx - 1]
+    ball = np.flatnonzero(d <= r)
+
+    def farthest(sel):
+        far = d[sel].max()
+        return sel[d[sel] == far], far.item()
+
+    horizontal, dh = farthest(ball)
+    upper, du = farthest(ball[k[ball] == k[ball].min()])      # the fewest clusters
+    lower, dl = farthest(ball[k[ball] == k[ball].max()])      # the most clusters
+    return {"ball": ball, "horizontal": horizontal, "upper_vertical": upper, "lower_vertical": lower,
+            "radius": r.item(), "horizontal_distance": dh, "upper_vertical_distance": du,
+            "lower_vertical_distance": dl}
+
+
+def credible_ball(trace: LabelTrace, cl, dist: str = "VI", alpha: float = 0.05) -> dict:
+    """mcclust.ext::credibleball(c.star, cls.draw, c.dist, alpha) from a ``LabelTrace``: the
+    smallest ball around the estimate ``cl``, in the VI or Binder distance (``dist`` "VI" or
+    "Binder"; the latter as the count of disagreeing pairs), that holds a share 1 - alpha of
+    the saved draws, and its three bounds.  With d the M distances of ``LabelTrace.distances``
+    and r the ceil((1 - alpha) M)-th smallest, the ball is the draws with d <= r; the
+    horizontal bound is the ball's draws at the largest distance, the upper vertical bound
+    those at the largest distance among the ball's draws with the fewest clusters, the lower
+    vertical bound the same among those with the most clusters.  All ties are returned.
+
+    The result holds draw indices (the caller keeps the draws): "ball", "horizontal",
+    "upper_vertical", "lower_vertical"; and "radius", "horizontal_distance",
+    "upper_vertical_distance", "lower_vertical_distance" and "distances" (the M values).
+    R is absent here, so parity with the package (its handling of ties at the radius
+    included) is unpinned, as minVI's is."""
+    if not isinstance(trace, LabelTrace):
+        raise ValueError("credible_ball needs a LabelTrace")
+    if dist not in ("VI", "Binder"):
+        raise ValueError(f"unknown distance {dist!r}")
+    c = trace._one(cl)
+    vi, binder, k = trace.distances(c)
+    d = vi[0] if dist == "VI" else binder[0]
+    out = _ball(d, k, alpha)
+    out["distances"] = d
+    return out
 
 
 def arandi(cl1, cl2, adjust: bool = True) -> float:

@@ -26,6 +26,18 @@ minvi_avg end to end on a fresh trace.  The dense path (PSM + scipy's linkage on
 matrix) is timed beside it on --dense-n evenly spaced points of the same trace (default 4,000;
 0 = skip; the full C4 matrix would be 39 GB of doubles on the host and a 70k-point
 linkage), with the two partitions compared.
+
+    python tools/trace_summary_bench.py --uncertainty
+    python tools/trace_summary_bench.py --run unc-c4 | unc-c5
+
+--uncertainty: how far the estimate can be trusted (LabelTrace.distances / affinity,
+csrc/trace_uncertainty.hip) on the recorded chains of --avg, unc-c5 (N = 1,000,000, M = 64)
+being the headline; the estimate is minvi_avg's.  One JSON line per run with the medians (and
+the smallest and largest) of --reps timed C calls after one warm-up call, labels already
+int32 and relabelled: `terms` for the estimate alone, `affinity` (aff only, N x Ka uint64
+copied back), `cross` (cross only), both together, and `distances` beside `losses` (VI and
+Binder) for the same 8 draws as candidates; "table_reads_TBps" is M N Ka x 4 B over the
+`affinity` median.
 """
 import argparse
 import json
@@ -39,6 +51,7 @@ sys.path.insert(0, ROOT)
 
 RUNS = {"c4": 600, "c5": 420}       # seconds allowed per run
 AVG_RUNS = {"avg-c4": 420, "avg-c5": 420, "avg-synth": 420}
+UNC_RUNS = {"unc-c4": 300, "unc-c5": 420}
 
 
 def labels(N, M, seed):
@@ -195,6 +208,54 @@ def run_avg(name, dense_n):
     print(json.dumps(res), flush=True)
 
 
+def run_unc(name, reps):
+    import numpy as np
+    from split_and_merge_gibbs_sampling_amd._lib import ptr
+    from split_and_merge_gibbs_sampling_amd.posterior import LabelTrace, _relabel, minvi_avg
+    free_bytes()
+    cfg, M = ("c4", 24) if name == "unc-c4" else ("c5", 64)
+    tr = np.ascontiguousarray(_relabel(chain_trace(cfg, M), "iteration"))
+    N = tr.shape[1]
+    f0 = free_bytes()
+    t = LabelTrace(tr)
+    cl = np.ascontiguousarray(minvi_avg(t)[0][None, :] - 1, dtype=np.int32)
+    Ka = int(cl.max()) + 1
+    cands = np.ascontiguousarray(tr[:: max(1, M // 8)][:8])
+    nc = len(cands)
+    L, h, chk = t.eng._L, t.eng._h, t.eng._check
+    all_, same = np.zeros(N, np.uint64), np.zeros((1, N), np.uint64)
+    aff, cross = np.zeros((N, Ka), np.uint64), np.zeros((Ka, Ka), np.uint64)
+    vi, b, k = np.zeros((nc, M)), np.zeros((nc, M), np.uint64), np.zeros(M, np.int32)
+    lv, lq, lp = np.zeros(nc), np.zeros(nc, np.uint64), np.zeros(1, np.uint64)
+    calls = {
+        "terms": lambda: L.hdpm_trace_terms(h, ptr(cl), 1, ptr(all_), ptr(same)),
+        "affinity": lambda: L.hdpm_trace_affinity(h, ptr(cl), Ka, ptr(aff), None),
+        "cross": lambda: L.hdpm_trace_affinity(h, ptr(cl), Ka, None, ptr(cross)),
+        "affinity_and_cross": lambda: L.hdpm_trace_affinity(h, ptr(cl), Ka, ptr(aff), ptr(cross)),
+        "distances": lambda: L.hdpm_trace_distances(h, ptr(cands), nc, ptr(vi), ptr(b), ptr(k)),
+        "losses": lambda: L.hdpm_trace_losses(h, ptr(cands), nc, None, ptr(lv), ptr(lq), ptr(lp)),
+    }
+    res = {"run": name, "N": N, "M": M, "Ka": Ka, "Kz": int(tr.max()) + 1, "ncand_distances": nc, "reps": reps}
+    for key, call in calls.items():
+        chk(call())                                  # warm-up: buffers allocated
+        ts = []
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            chk(call())
+            ts.append(time.perf_counter() - t0)
+        ts.sort()
+        res[key + "_s"] = {"median": round(ts[len(ts) // 2], 6), "min": round(ts[0], 6), "max": round(ts[-1], 6)}
+    res["table_reads_TBps"] = round(M * N * Ka * 4 / res["affinity_s"]["median"] / 1e12, 4)
+    res["affinity_over_terms"] = round(res["affinity_s"]["median"] / res["terms_s"]["median"], 3)
+    res["distances_over_losses"] = round(res["distances_s"]["median"] / res["losses_s"]["median"], 3)
+    res["device_bytes"] = int(f0 - free_bytes())
+    # what was timed is right: aff's row sums are `all`, its own column is `same`
+    assert np.array_equal(aff.sum(1), all_) and np.array_equal(aff[np.arange(N), cl[0]], same[0])
+    assert np.array_equal(cross, cross.T) and int(cross.sum()) == int(all_.sum())
+    t.close()
+    print(json.dumps(res), flush=True)
+
+
 def C_groups(t):
     import ctypes
     U = ctypes.c_int32(0)
@@ -205,10 +266,17 @@ def C_groups(t):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--run", choices=sorted(RUNS) + sorted(AVG_RUNS))
+    ap.add_argument("--run", choices=sorted(RUNS) + sorted(AVG_RUNS) + sorted(UNC_RUNS))
+    ap.add_argument("--uncertainty", action="store_true", help="distances and affinities on recorded chains")
+    ap.add_argument("--reps", type=int, default=7, help="--uncertainty: timed calls per quantity (at least 5)")
     ap.add_argument("--avg", action="store_true", help="the matrix-free average-linkage search on recorded chains")
     ap.add_argument("--dense-n", type=int, default=4000, help="--avg: points of the dense comparison (0: none)")
     a = ap.parse_args()
+    if a.reps < 5:
+        ap.error("--reps must be at least 5")
+    if a.run in UNC_RUNS:
+        run_unc(a.run, a.reps)
+        return 0
     if a.run in AVG_RUNS:
         run_avg(a.run, a.dense_n)
         return 0
@@ -216,8 +284,8 @@ def main():
         run(a.run)
         return 0
     # the parent never opens the GPU; a run that fails or overruns ends the tool
-    for name, limit in (AVG_RUNS if a.avg else RUNS).items():
-        extra = ["--dense-n", str(a.dense_n)] if a.avg else []
+    for name, limit in (UNC_RUNS if a.uncertainty else AVG_RUNS if a.avg else RUNS).items():
+        extra = ["--reps", str(a.reps)] if a.uncertainty else ["--dense-n", str(a.dense_n)] if a.avg else []
         st = subprocess.run(["timeout", "-k", "10", str(limit), sys.executable, "-u", os.path.abspath(__file__),
                              "--run", name] + extra).returncode
         if st != 0:
