@@ -34,6 +34,7 @@
 #include "host_topology.hpp"
 #include "kernels.hpp"
 #include "mtjump.hpp"
+#include "phi_host.hpp"
 #include "pool_host.hpp"
 #include "rmath.hpp"
 #include "trace_tree.hpp"
@@ -3919,7 +3920,6 @@ struct Ctx {
     hipEvent_t ev_last = nullptr;
     hipStream_t last_s = nullptr;
     bool fast_out(const uint8_t* o) const { return o && (o == out2[0].p || o == out2[1].p); }
-    int64_t fast_calls = 0;
     // tree mode when every updated cluster has at least this many members (a small cluster's
     // center picks can depend on the uniform); raised past a cluster size that needed a retry
     int tree_min_count = 16;
@@ -3939,8 +3939,6 @@ struct Ctx {
       p = std::min(hi, std::max(hi > 0.3 ? 0.02 : 0.05, 0.7 * p + 0.3 * ph));
     }
     static void widen(double& p, double hi = 0.3) { p = std::min(hi, 1.5 * p + 0.05); }
-    int64_t calls = 0, fallbacks = 0;
-    int last_status = 0;
   } phd;
   // update_phi placement: the host job speculated during the sweep (default), or the device
   // (phi.hip, after the sweep): HDPM_OPT_PHI_DEVICE, or HDPM_PHI=device in the environment;
@@ -4002,8 +4000,9 @@ struct Ctx {
 
   // update_phi (cf:511-591) of the labels in mask on the device.  Returns kOk when committed
   // (new centers / sigmas in h_center / h_sigma and in the device tables, the host stream
-  // past the update's draws), -1 when the device path does not apply or met a case it
-  // leaves to the host (nothing changed: same stream position, same tables).
+  // past the update's draws), -1 when the device path does not apply, kPhiHandedBack when it
+  // met a case it leaves to the host (either way nothing changed: same stream position, same
+  // tables).
   // Sizes of a device update of T clusters (phi.hip): drift windows (kernels.hpp phi_lo /
   // phi_hi, from the rate and spread of the extra uniforms per sigma draw), mask words per
   // candidate, start drifts walked per cluster, stream words read, walk workgroup shape.
@@ -4150,6 +4149,55 @@ struct Ctx {
     }
     return pf;
   }
+  // the general kernels' composition trees, unless a cluster is small enough for a pick to depend
+  // on the uniform (with one walk segment per cluster, d <= 128, such clusters are walked inside
+  // the tree-mode update itself); debug bit 27: always the per-start-drift walks
+  bool phi_tree_for(const PhiPlan& pl, int min_count) const {
+    return pl.tree_ok && (pl.S == 1 || min_count >= phd.tree_min_count) && !(debug & 134217728);
+  }
+
+  // ---- the outcome of one device update (phi_host.hpp: PhiOutView, phi_rerun_mode) ----
+  static_assert(phi_host::kOk == kPhiOk && phi_host::kWindow == kPhiWindow && phi_host::kShort == kPhiShort &&
+                phi_host::kNonDet == kPhiNonDet, "phi_host.hpp's statuses are kernels.hpp's");
+  // A pick depended on the uniform (kPhiNonDet): updates with clusters this small take the
+  // walks directly from now on (tree mode), or the fast path rests for kFastBackoff updates.
+  void phi_note_nondet(bool fast, int min_count) {
+    if (fast) phd.fast_backoff = PhiDevice::kFastBackoff;
+    else phd.tree_min_count = std::max(phd.tree_min_count, std::min(1 << 20, 2 * min_count));
+  }
+  // device_update_phi / dspec_commit: the device ran the update and handed it back (-1: nothing ran)
+  static constexpr int kPhiHandedBack = -2;
+  // A handed-back update's mask bit.  One update counts once, as a device call or a fallback, where
+  // its outcome is decided: no `count` for an attempt another may follow (a wider window, a re-run).
+  void phi_note_handback(int status, bool count) {
+    stats.phi_fallback_status_mask |= phi_handback_bit(status);
+    if (count) stats.phi_device_fallbacks++;
+  }
+  // The ladder of device_update_phi and split-merge's updates.  run(mode) enqueues the update
+  // by these kernels, waits for it and returns its status; the last run's is returned.
+  template <class Run>
+  int phi_ladder(const PhiPlan& pl, bool fast, int min_count, Run&& run) {
+    const bool tree = phi_tree_for(pl, min_count);
+    const int mode = fast ? phi_host::kFast : tree ? phi_host::kTree : phi_host::kWalks;
+    int status = run(mode);
+    if (mode == phi_host::kTree) stats.phi_tree_calls++;
+    if (fast && status != kPhiOk) stats.phi_fast_handbacks++;
+    const int again = phi_rerun_mode(mode, status, tree);
+    if (again != phi_host::kNoRerun) {
+      if (status == kPhiNonDet) {
+        phi_note_nondet(fast, min_count);
+        stats.phi_tree_retries++;
+      }
+      status = run(again);
+    }
+    return status;
+  }
+  // The committed update's parameters on the host: centers and sigmas of its T clusters into
+  // rows labels[t] (null: row t) of h_center / h_sigma; returns compute_loglikelihood's sum.
+  double phi_commit_host(const PhiOutView& v, int T, const int* labels) {
+    phi_copy_params(v, T, d, labels, h_center.data(), h_sigma.data());
+    return phi_ll_fold(v.ll(), T);
+  }
 
   // Enqueue one device update of T clusters on stream s: labels / counts / current sigmas in,
   // status + consumption, picks, sigmas and log-likelihood pairs out (phi_out_layout) in the
@@ -4165,8 +4213,7 @@ struct Ctx {
                              const RngWindow* chainW = nullptr, int64_t sweep_len = 0) {
     const int T = pl.T;
     const int64_t items = pl.items;
-    size_t o_pick, o_sig, o_ll, bytes;
-    phi_out_layout(T, d, &o_pick, &o_sig, &o_ll, &bytes);
+    const PhiOutLayout L = phi_out_layout(T, d);
     if (phd.last_s && phd.last_s != s) HIPCHK(hipStreamWaitEvent(s, phd.ev_last, 0));
     if (!phd.ev_last) HIPCHK(hipEventCreateWithFlags(&phd.ev_last, hipEventDisableTiming));
     phd.last_s = s;
@@ -4181,11 +4228,10 @@ struct Ctx {
     a.stage = phd.stage.p;
     const size_t o_sigin = align16((size_t)2 * T * 4), in_bytes = o_sigin + (size_t)items * 8;
     if (mode == 2) {
-      const size_t o_state = align16(bytes);             // the stream state after the update
       const int sl = phd.slot;
       phd.slot ^= 1;
       PinBuf<uint8_t>& hout = phd.out2[sl];
-      hout.ensure(o_state + 625 * 4 + 64, hipHostMallocCoherent);
+      hout.ensure(L.o_state + 625 * 4 + 64, hipHostMallocCoherent);   // with the stream state after the update
       phd.stage2[sl].ensure(upload_layout(T, dp, d, bw).bytes);
       a.stage = phd.stage2[sl].p;
       phd.labc2[sl].ensure(2 * T);
@@ -4237,11 +4283,11 @@ struct Ctx {
       }
       // (w2, the release of phd's buffers by the sweep's stream, guards the staging buffer:
       // only k_phi2_values writes it, so only it waits)
-      a.pick = hout.p + o_pick;
-      a.sig_out = (double*)(hout.p + o_sig);
-      a.ll = (double*)(hout.p + o_ll);
+      a.pick = hout.p + L.o_pick;
+      a.sig_out = (double*)(hout.p + L.o_sig);
+      a.ll = (double*)(hout.p + L.o_ll);
       a.status_host = (int*)hout.p;
-      a.state_host = a.raw_ptr == nullptr && (chainW || a.mti_pos >= 1) ? (uint32_t*)(hout.p + o_state) : nullptr;
+      a.state_host = a.raw_ptr == nullptr && (chainW || a.mti_pos >= 1) ? (uint32_t*)(hout.p + L.o_state) : nullptr;
       if (a.state_host) a.state_host[624] = 0;
       a.gs = pl.gs; a.G = pl.G; a.gtab2 = phd.gtab2.p; a.roots = phd.roots.p; a.ctr = phd.ctr.p; a.gen = phd.gen;
       a.tree = nullptr;
@@ -4254,7 +4300,6 @@ struct Ctx {
       }
       HIPCHK(launch_phi2(a, s, w2));
       HIPCHK(hipEventRecord(phd.ev_last, s));
-      phd.fast_calls++;
       stats.phi_fast_calls++;
       return hout.p;
     }
@@ -4263,7 +4308,7 @@ struct Ctx {
     a.stage = phd.stage.p;
     a.chain_in = nullptr; a.chain_out = nullptr; a.sig_dev = nullptr;
     phd.h_in.ensure(in_bytes + 64);
-    phd.h_out.ensure(bytes);
+    phd.h_out.ensure(L.bytes);
     int* hl = (int*)phd.h_in.p;
     std::memcpy(hl, lab, (size_t)T * 4);
     std::memcpy(hl + T, cnt, (size_t)T * 4);
@@ -4286,9 +4331,9 @@ struct Ctx {
     HIPCHK(hipMemsetAsync(phd.act.p, 0, 4, s));
     HIPCHK(launch_phi(a, s));
     HIPCHK(hipMemcpyAsync(phd.h_out.p, phd.status.p, 16, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(phd.h_out.p + o_pick, phd.pick.p, (size_t)items, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(phd.h_out.p + o_sig, phd.sig_out.p, (size_t)items * 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(phd.h_out.p + o_ll, phd.ll.p, (size_t)2 * T * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(phd.h_out.p + L.o_pick, phd.pick.p, (size_t)items, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(phd.h_out.p + L.o_sig, phd.sig_out.p, (size_t)items * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(phd.h_out.p + L.o_ll, phd.ll.p, (size_t)2 * T * 8, hipMemcpyDeviceToHost, s));
     HIPCHK(hipEventRecord(phd.ev_last, s));
     return phd.h_out.p;
   }
@@ -4322,76 +4367,53 @@ struct Ctx {
     auto tp0 = std::chrono::steady_clock::now();
     histogram_launch(nidx == 0 ? nullptr : &mask);
     const unsigned* fsrc = nidx == 0 ? d_freq.p : d_freq_m.p;
-    // inputs: labels, counts, current sigmas
-    std::vector<int> labs(T), cnts(T);
+    // inputs: labels (touched), counts, current sigmas
+    std::vector<int> cnts(T);
     std::vector<double> sigs((size_t)items);
     for (int t = 0; t < T; ++t) {
-      labs[t] = touched[t];
       cnts[t] = h_counts[touched[t]];
       std::memcpy(&sigs[(size_t)t * d], &h_sigma[(size_t)touched[t] * d], (size_t)d * 8);
     }
-    size_t o_pick, o_sig, o_ll, obytes;
-    phi_out_layout(T, d, &o_pick, &o_sig, &o_ll, &obytes);
+    const PhiOutLayout L = phi_out_layout(T, d);
     const uint8_t* out = nullptr;
     uint8_t* out_stage = nullptr;      // the staged tables of the update that produced `out`
-    auto run = [&](int mode) {
+    bool first = true;
+    const int status = phi_ladder(pl, fast, min_count, [&](int mode) {
       const PhiPlan& pm = mode == 2 ? pf : pl;
       PhiArgs a = phi_args(pm);
       a.freq = fsrc;
       phi_raw(a, *W);
-      out = enqueue_phi(a, pm, mode, labs.data(), cnts.data(), sigs.data(), stream, W->done);
+      out = enqueue_phi(a, pm, mode, touched.data(), cnts.data(), sigs.data(), stream, W->done);
       out_stage = a.stage;
-    };
-    // the fast path, else the composition trees unless a cluster is small enough for a pick to
-    // depend on the uniform (debug bit 27: always the per-start-drift walks)
-    // (with one walk segment per cluster, d <= 128, such clusters are walked inside the tree-mode
-    // update itself)
-    const bool tree = pl.tree_ok && (pl.S == 1 || min_count >= phd.tree_min_count) && !(debug & 134217728);
-    run(fast ? 2 : tree ? 1 : 0);
-    histogram_wait(nidx == 0 ? nullptr : &mask);
-    if (freq_next_pending) {
-      std::swap(h_freq.p, h_freq_next.p);
-      std::swap(h_freq.n, h_freq_next.n);
-      freq_next_pending = false;
-    }
-    HIPCHK(hipStreamSynchronize(stream));
-    phd.calls++;
-    if (tree && !fast) stats.phi_tree_calls++;
-    if (fast && phd.tdbg.p && std::getenv("HDPM_PHI_TIMING")) {
-      unsigned long long m[24];
-      HIPCHK(hipMemcpy(m, phd.tdbg.p, sizeof(m), hipMemcpyDeviceToHost));
-      std::string line = "[phi2 us]";
-      for (int q = 1; q < 23; ++q) {
-        char b[32];
-        std::snprintf(b, sizeof(b), " %d:%.2f", q, m[q] && m[0] ? (double)(long long)(m[q] - m[0]) * 0.01 : -1.0);
-        line += b;
+      if (first) histogram_wait(nidx == 0 ? nullptr : &mask);
+      if (first && freq_next_pending) {
+        std::swap(h_freq.p, h_freq_next.p);
+        std::swap(h_freq.n, h_freq_next.n);
+        freq_next_pending = false;
       }
-      std::fprintf(stderr, "%s\n", line.c_str());
-    }
-    if (std::getenv("HDPM_PHI_TRACE"))
-      std::fprintf(stderr, "[phi] T %d nw %d tW %d fast_ok %d gs %d G %d min_count %d tree_min %d fast %d tree %d status %d\n",
-                   T, pl.nw, pl.tW, (int)pl.fast_ok, pl.gs, pl.G, min_count, phd.tree_min_count, (int)fast, (int)tree,
-                   ((const int*)out)[0]);
-    if (fast && ((const int*)out)[0] != kPhiOk) stats.phi_fast_handbacks++;
-    if ((fast || tree) && ((const int*)out)[0] == kPhiNonDet) {
-      // a pick depends on the uniform: the same update by the walks (same inputs, nothing
-      // committed yet); updates with clusters this small take the walks directly from now on
-      if (fast) phd.fast_backoff = PhiDevice::kFastBackoff;
-      else phd.tree_min_count = std::max(phd.tree_min_count, std::min(1 << 20, 2 * min_count));
-      stats.phi_tree_retries++;
-      run(0);
       HIPCHK(hipStreamSynchronize(stream));
-    } else if (fast && ((const int*)out)[0] != kPhiOk && ((const int*)out)[0] != kPhiWindow &&
-               ((const int*)out)[0] != kPhiShort) {
-      // a case the fast path leaves to the general kernels (the bisection path, ...)
-      run(tree ? 1 : 0);
-      HIPCHK(hipStreamSynchronize(stream));
-    }
-    const int status = ((const int*)out)[0];
+      const int st = PhiOutView(out, L).status();
+      if (first && fast && phd.tdbg.p && std::getenv("HDPM_PHI_TIMING")) {
+        unsigned long long m[24];
+        HIPCHK(hipMemcpy(m, phd.tdbg.p, sizeof(m), hipMemcpyDeviceToHost));
+        std::string line = "[phi2 us]";
+        for (int q = 1; q < 23; ++q) {
+          char b[32];
+          std::snprintf(b, sizeof(b), " %d:%.2f", q, m[q] && m[0] ? (double)(long long)(m[q] - m[0]) * 0.01 : -1.0);
+          line += b;
+        }
+        std::fprintf(stderr, "%s\n", line.c_str());
+      }
+      if (first && std::getenv("HDPM_PHI_TRACE"))
+        std::fprintf(stderr, "[phi] T %d nw %d tW %d fast_ok %d gs %d G %d min_count %d tree_min %d fast %d tree %d status %d\n",
+                     T, pl.nw, pl.tW, (int)pl.fast_ok, pl.gs, pl.G, min_count, phd.tree_min_count, (int)fast,
+                     (int)phi_tree_for(pl, min_count), st);
+      first = false;
+      return st;
+    });
+    const PhiOutView res(out, L);
     stats.phi_device_last_status = status;
-    int64_t cons = 0;
-    std::memcpy(&cons, out + 8, 8);
-    phd.last_status = status;
+    const int64_t cons = res.cons();
     const uint64_t target = rng.pos + (uint64_t)cons;
     if ((debug & 2) && !fast) {
       std::vector<int64_t> dts(T);
@@ -4415,38 +4437,23 @@ struct Ctx {
     }
     if (status != kPhiOk || cons <= 0 || !can_adopt(*W, target)) {
       phd_release(stream);
-      phd.fallbacks++;
-      stats.phi_device_fallbacks++;
-      stats.phi_fallback_status_mask |= (int64_t)1 << (status != kPhiOk ? std::min(std::max(status, 0), 14) : 15);
+      phi_note_handback(status, true);
       if (status == kPhiOk) stats.phi_device_last_status = -1;
-      return -1;
+      return kPhiHandedBack;
     }
     stats.phi_device_calls++;
     // commit: tables on the device, parameters on the host, the stream past the draws
     HIPCHK(launch_scatter_clusters(out_stage, T, dp, d, bw, full ? 1 : 0, d_slot_codes.p, d_slot_tab.p, d_slot_bnd.p,
                                    d_counts.p, d_sol.p, d_los.p, d_src.p, stream));
     phd_release(stream);
-    const uint8_t* pk = out + o_pick;
-    const double* sg = (const double*)(out + o_sig);
-    const double* ll = (const double*)(out + o_ll);
-    double hi = 0.0, lo = 0.0;
-    for (int t = 0; t < T; ++t) {
-      const int k = touched[t];
-      for (int j = 0; j < d; ++j) h_center[(size_t)k * d + j] = (uint8_t)(pk[(size_t)t * d + j] + 1);
-      std::memcpy(&h_sigma[(size_t)k * d], sg + (size_t)t * d, (size_t)d * 8);
-      for (int q = 0; q < 2; ++q) {
-        const double x = ll[2 * t + q], s = hi + x;
-        lo += std::fabs(hi) >= std::fabs(x) ? (hi - s) + x : (x - s) + hi;
-        hi = s;
-      }
-    }
+    const double ll = phi_commit_host(res, T, touched.data());
     if (full) {
-      dev_ll = hi + lo;
+      dev_ll = ll;
       dev_ll_version = labels_version;
       tables_dirty = false;
     }
     stage_full = false;                // the host staging no longer mirrors the device tables
-    adopt_after_phi(*W, target, phd.fast_out(out) ? (const uint32_t*)(out + phi_state_off(T, d)) : nullptr);
+    adopt_after_phi(*W, target, phd.fast_out(out) ? res.state_words() : nullptr);
     // the drift model follows the chain: extra uniforms per sigma draw seen here
     PhiDevice::adapt(phd.p_rej, cons - 3 * items, items);
     stats.t_host_phi_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tp0).count();
@@ -4471,14 +4478,12 @@ struct Ctx {
     PhiPlan pl;
     RngWindow* W = nullptr;
     bool tree = false;
-    size_t o_pick = 0, o_sig = 0, o_ll = 0;
     const uint8_t* out = nullptr;      // its outputs (phd.h_out, or phd.out2[slot] on the fast path)
     bool fast = false;
-    hipEvent_t ev = nullptr;           // they are complete
+    hipEvent_t ev = nullptr;           // they are complete (created once, kept across launches)
     uint8_t* stage = nullptr;          // its staged tables
     int gen = 0;                       // fast path: its status generation
     int prev_gen = 0;                  // chained: the update it follows
-    uint64_t est_pos = 0;              // chained: its nominal first position (when launched)
     uint64_t wgen = 0;                 // W's generation when launched
     int64_t sweep_len = 0;             // chained: the sweep's draws before it
     PhiChain* chain = nullptr;         // fast path: its chain word (end position, completion)
@@ -4500,6 +4505,8 @@ struct Ctx {
       // the fast path's last workgroup writes the status word last (system-scope release, after
       // every other output and after every other workgroup finished): spin on it instead of a
       // blocking event wait (whose wake-up alone costs tens of microseconds); 2 s, then the event
+      // (the raw acquire load, not PhiOutView::status(): the view reads a completed update,
+      // this load is what makes the device's other outputs visible before they are read)
       const auto t0 = std::chrono::steady_clock::now();
       for (int polls = 0;; ++polls) {
         if (__atomic_load_n((const int*)dspec.out, __ATOMIC_ACQUIRE) != -1) break;
@@ -4515,20 +4522,25 @@ struct Ctx {
     }
     dspec.inflight = false;
   }
-  // outputs of a device update of T clusters in phd.h_out: status + consumption, picks, sigmas,
-  // log-likelihood pairs
-  static void phi_out_layout(int T, int d_, size_t* o_pick, size_t* o_sig, size_t* o_ll, size_t* bytes) {
-    const size_t items = (size_t)T * d_;
-    *o_pick = 16;
-    *o_sig = align16(*o_pick + items);
-    *o_ll = *o_sig + items * 8;
-    *bytes = *o_ll + (size_t)2 * T * 8;
-  }
-  // (the fast path's copy of the stream state follows them)
-  static size_t phi_state_off(int T, int d_) {
-    size_t o_pick, o_sig, o_ll, bytes;
-    phi_out_layout(T, d_, &o_pick, &o_sig, &o_ll, &bytes);
-    return align16(bytes);
+  // The record of the update just enqueued on pstream with outputs `out`, its completion marked by
+  // the record's long-lived event ev; the fields it leaves at their defaults are the caller's.
+  DevSpec dev_record(hipEvent_t ev, const uint8_t* out, const PhiArgs& a, const PhiPlan& pl, RngWindow* W, bool fast) {
+    if (!ev) HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    HIPCHK(hipEventRecord(ev, pstream));
+    DevSpec r;
+    r.ran = r.inflight = true;
+    r.epoch = rng.epoch;
+    r.K = K;
+    r.pl = pl;
+    r.W = W;
+    r.wgen = W->gen;
+    r.out = out;
+    r.fast = fast;
+    r.ev = ev;
+    r.stage = a.stage;
+    r.gen = fast ? a.gen : 0;
+    r.chain = fast ? a.chain_out : nullptr;
+    return r;
   }
 
   void dspec_launch() {
@@ -4551,35 +4563,18 @@ struct Ctx {
     dspec_wait();                      // phd.h_in / h_out are free on the host
     PhiArgs a = phi_args(pl);
     const int T = K;
-    size_t bytes;
-    phi_out_layout(T, d, &dspec.o_pick, &dspec.o_sig, &dspec.o_ll, &bytes);
     std::vector<int> labs(T);
     for (int t = 0; t < T; ++t) labs[t] = t;
-    if (!dspec.ev) HIPCHK(hipEventCreateWithFlags(&dspec.ev, hipEventDisableTiming));
-
     a.freq = d_freq.p;
     phi_raw(a, *W);
-    const bool tree = pl.tree_ok && (pl.S == 1 || min_count >= phd.tree_min_count) && !(debug & 134217728);
+    const bool tree = phi_tree_for(pl, min_count);
     dnext.ran = false;                 // (a chained update still queued completes unused)
-    dspec.out = enqueue_phi(a, pl, fast ? 2 : tree ? 1 : 0, labs.data(), h_counts.data(), h_sigma.data(), pstream,
-                            W->done, ev_phd_free);
-    HIPCHK(hipEventRecord(dspec.ev, pstream));
-    dspec.stage = a.stage;
-    dspec.gen = fast ? a.gen : 0;
-    dspec.prev_gen = 0;
-    dspec.wgen = W->gen;
-    dspec.chain = fast ? a.chain_out : nullptr;
-    dspec.ran = true;
-    dspec.inflight = true;
-    dspec.pos = rng.pos;
-    dspec.epoch = rng.epoch;
-    dspec.lv = 0;
-    dspec.K = K;
-    dspec.moves = -1;
-    dspec.pl = pl;
-    dspec.W = W;
-    dspec.tree = tree && !fast;
-    dspec.fast = fast;
+    const uint8_t* out = enqueue_phi(a, pl, fast ? 2 : tree ? 1 : 0, labs.data(), h_counts.data(), h_sigma.data(),
+                                     pstream, W->done, ev_phd_free);
+    DevSpec r = dev_record(dspec.ev, out, a, pl, W, fast);   // (lv, moves: set at the sweep's end)
+    r.pos = rng.pos;
+    r.tree = tree && !fast;
+    dspec = r;
     stats.phi_dspec_launched++;
   }
 
@@ -4616,30 +4611,11 @@ struct Ctx {
     if (!W) return;
     PhiArgs a = phi_args(pl);
     a.freq = d_freq.p;
-    if (!dnext.ev) HIPCHK(hipEventCreateWithFlags(&dnext.ev, hipEventDisableTiming));
-    dnext.out = enqueue_phi(a, pl, 2, nullptr, nullptr, nullptr, pstream, W->done, ev_phd_free, W, sweep_len);
-    HIPCHK(hipEventRecord(dnext.ev, pstream));
-    dnext.ran = true;
-    dnext.inflight = true;
-    dnext.pos = 0;                     // (known when dspec's update is committed)
-    dnext.epoch = rng.epoch;
-    dnext.lv = 0;
-    dnext.K = K;
-    dnext.moves = -1;
-    dnext.pl = pl;
-    dnext.W = W;
-    dnext.wgen = W->gen;
-    dnext.tree = false;
-    dnext.fast = true;
-    dnext.stage = a.stage;
-    dnext.chain = a.chain_out;
-    dnext.gen = a.gen;
-    dnext.prev_gen = dspec.gen;
-    dnext.est_pos = lo;
-    dnext.sweep_len = sweep_len;
-    dnext.o_pick = dspec.o_pick;
-    dnext.o_sig = dspec.o_sig;
-    dnext.o_ll = dspec.o_ll;
+    const uint8_t* out = enqueue_phi(a, pl, 2, nullptr, nullptr, nullptr, pstream, W->done, ev_phd_free, W, sweep_len);
+    DevSpec r = dev_record(dnext.ev, out, a, pl, W, true);   // (pos: known when dspec's update is committed)
+    r.prev_gen = dspec.gen;
+    r.sweep_len = sweep_len;
+    dnext = r;
     stats.phi_chain_launched++;
   }
   // pipe_go (the sweep enqueued ahead goes, dspec's update committed): the chained update
@@ -4674,31 +4650,23 @@ struct Ctx {
     phd_release(stream);
   }
 
-  // update_phi from the speculation (after a sweep without moves): kOk, or -1 when it did not
-  // complete on the device (the caller runs the update; nothing was changed).
+  // update_phi from the speculation (after a sweep without moves): kOk; kPhiHandedBack when it did
+  // not complete on the device (nothing was changed; no re-run and no count here: the caller runs
+  // the update and counts, update_phi); or -1 with err set.
   int dspec_commit() {
     dspec_wait();
     dspec.ran = false;
-    phd.calls++;
     if (dspec.tree) stats.phi_tree_calls++;
     const int T = dspec.K;
-    const int status = ((const int*)dspec.out)[0];
+    const PhiOutView res(dspec.out, phi_out_layout(T, d));
+    const int status = res.status();
     if (dspec.fast && status != kPhiOk) stats.phi_fast_handbacks++;
     if (std::getenv("HDPM_PHI_TRACE"))
       std::fprintf(stderr, "[phi dspec] T %d fast %d status %d\n", T, (int)dspec.fast, status);
     stats.phi_device_last_status = status;
-    int64_t cons = 0;
-    std::memcpy(&cons, dspec.out + 8, 8);
+    const int64_t cons = res.cons();
     const uint64_t target = rng.pos + (uint64_t)cons;
-    if (status == kPhiNonDet) {
-      if (dspec.fast) {
-        phd.fast_backoff = PhiDevice::kFastBackoff;
-      } else {
-        int mc = INT_MAX;
-        for (int k = 0; k < T; ++k) mc = std::min(mc, h_counts[k]);
-        phd.tree_min_count = std::max(phd.tree_min_count, std::min(1 << 20, 2 * mc));
-      }
-    }
+    if (status == kPhiNonDet) phi_note_nondet(dspec.fast, *std::min_element(h_counts.begin(), h_counts.begin() + T));
     // a sweep the device already started behind this update (PipeAuto) is followed: the update
     // completed with its stream state (the chain word), so the host takes it as it is
     const bool followed = pre_dev_decision() == 1;
@@ -4711,16 +4679,13 @@ struct Ctx {
     }
     if (!followed && (status != kPhiOk || cons <= 0 || !dspec.W || dspec.W->gen != dspec.wgen ||
                       !can_adopt(*dspec.W, target) || !covers(*dspec.W, rng.pos, dspec.pl.need))) {
-      phd.fallbacks++;
-      stats.phi_device_fallbacks++;
-      stats.phi_fallback_status_mask |= (int64_t)1 << (status != kPhiOk ? std::min(std::max(status, 0), 14) : 15);
-      return -1;
+      phi_note_handback(status, false);
+      return kPhiHandedBack;
     }
     stats.phi_device_calls++;
     stats.phi_dspec_used++;
     if (dspec.prev_gen) stats.phi_chain_used++;
     committed_gen = dspec.fast ? dspec.gen : 0;
-    const uint32_t* st_words = dspec.fast ? (const uint32_t*)(dspec.out + phi_state_off(T, d)) : nullptr;
     // tables: by the sweep enqueued ahead (its gated scatter, pipe_go), flush_commit, or now
     if (defer_commit) {
       commit_later.active = true;
@@ -4729,26 +4694,13 @@ struct Ctx {
     } else {
       scatter_dev_stage(T);
     }
-    const uint8_t* pk = dspec.out + dspec.o_pick;
-    const double* sg = (const double*)(dspec.out + dspec.o_sig);
-    const double* ll = (const double*)(dspec.out + dspec.o_ll);
-    double hi = 0.0, lo = 0.0;
-    for (int t = 0; t < T; ++t) {
-      for (int j = 0; j < d; ++j) h_center[(size_t)t * d + j] = (uint8_t)(pk[(size_t)t * d + j] + 1);
-      for (int q = 0; q < 2; ++q) {
-        const double x = ll[2 * t + q], s2 = hi + x;
-        lo += std::fabs(hi) >= std::fabs(x) ? (hi - s2) + x : (x - s2) + hi;
-        hi = s2;
-      }
-    }
-    std::memcpy(h_sigma.data(), sg, (size_t)T * d * 8);
-    dev_ll = hi + lo;
+    dev_ll = phi_commit_host(res, T, nullptr);
     dev_ll_version = labels_version;
     tables_dirty = false;
     stage_full = false;                // the host staging no longer mirrors the device tables
     freq_next_pending = false;
     freq_version = labels_version;
-    adopt_after_phi(*dspec.W, target, st_words);
+    adopt_after_phi(*dspec.W, target, dspec.fast ? res.state_words() : nullptr);
     PhiDevice::adapt(phd.p_rej, cons - 3 * dspec.pl.items, dspec.pl.items);
     return kOk;
   }
@@ -4768,19 +4720,14 @@ struct Ctx {
     // a drift past the window (a merged or freshly split cluster can reject far more attempts
     // than the chain's updates; nothing was consumed) is retried with a wider window
     for (int attempt = 0;; ++attempt) {
-      const int r = device_update_phi_sm_once(T, cnt, freq, sig_in, cen, sig);
-      if (r == 1 && attempt >= 2) {
-        phd.fallbacks++;
-        stats.phi_device_fallbacks++;
-        return -1;
-      }
+      const int r = device_update_phi_sm_once(T, cnt, freq, sig_in, cen, sig, attempt >= 2);
       if (r != 1) return r;
       stats.phi_sm_window_retries++;
     }
   }
-  // kOk, -1 (handed back), or 1: the drift left the window (widened for the next attempt)
+  // kOk, -1 (handed back), or 1 (never for the `last` attempt): the drift left the window, now wider
   int device_update_phi_sm_once(int T, const int* cnt, const unsigned* freq, const double* sig_in, uint8_t* cen,
-                                double* sig) {
+                                double* sig, bool last) {
     int min_count = INT_MAX;
     for (int t = 0; t < T; ++t) min_count = std::min(min_count, cnt[t]);
     const PhiPlan pl = phi_plan(T, true);
@@ -4797,64 +4744,44 @@ struct Ctx {
     std::memcpy(h_sm_freq.p, freq, fw * 4);
     std::vector<int> labs(T);
     for (int t = 0; t < T; ++t) labs[t] = t;
-    size_t o_pick, o_sig, o_ll, bytes;
-    phi_out_layout(T, d, &o_pick, &o_sig, &o_ll, &bytes);
+    const PhiOutLayout L = phi_out_layout(T, d);
     HIPCHK(hipMemcpyAsync(d_sm_freq.p, h_sm_freq.p, fw * 4, hipMemcpyHostToDevice, stream));
     const uint8_t* out = nullptr;
-    auto run = [&](int mode) {
+    const int status = phi_ladder(pl, fast, min_count, [&](int mode) {
       const PhiPlan& pm = mode == 2 ? pf : pl;
       PhiArgs a = phi_args(pm);
       a.freq = d_sm_freq.p;
       phi_raw(a, *W);
       out = enqueue_phi(a, pm, mode, labs.data(), cnt, sig_in, stream, W->done);
       HIPCHK(hipStreamSynchronize(stream));
-    };
-    const bool tree = pl.tree_ok && (pl.S == 1 || min_count >= phd.tree_min_count) && !(debug & 134217728);
-    run(fast ? 2 : tree ? 1 : 0);
-    phd.calls++;
-    if (tree && !fast) stats.phi_tree_calls++;
-    if (fast && ((const int*)out)[0] != kPhiOk) stats.phi_fast_handbacks++;
-    if ((fast || tree) && ((const int*)out)[0] == kPhiNonDet) {
-      if (fast) phd.fast_backoff = PhiDevice::kFastBackoff;
-      else phd.tree_min_count = std::max(phd.tree_min_count, std::min(1 << 20, 2 * min_count));
-      stats.phi_tree_retries++;
-      run(0);
-    } else if (fast && ((const int*)out)[0] != kPhiOk && ((const int*)out)[0] != kPhiWindow &&
-               ((const int*)out)[0] != kPhiShort) {
-      run(tree ? 1 : 0);
-    }
+      return PhiOutView(out, L).status();
+    });
     phd_release(stream);
-    const int status = ((const int*)out)[0];
+    const PhiOutView res(out, L);
     stats.phi_device_last_status = status;
-    int64_t cons = 0;
-    std::memcpy(&cons, out + 8, 8);
+    const int64_t cons = res.cons();
     const uint64_t target = rng.pos + (uint64_t)cons;
     if (status != kPhiOk || cons <= 0 || !can_adopt(*W, target)) {
-      stats.phi_fallback_status_mask |= (int64_t)1 << (status != kPhiOk ? std::min(std::max(status, 0), 14) : 15);
       if (status == kPhiOk) stats.phi_device_last_status = -1;
-      if (status != kPhiShort && status != kPhiWindow) {
-        phd.fallbacks++;
-        stats.phi_device_fallbacks++;
-      }
       if (std::getenv("HDPM_PHI_TRACE"))
         std::fprintf(stderr, "[phi sm] T %d items %lld need %lld nw %d p_rej %.4f status %d cons %lld counts %d %d\n", T,
                      (long long)items, (long long)pl.need, pl.nw, phd.p_rej_sm, status, (long long)cons, cnt[0],
                      T > 1 ? cnt[1] : -1);
+      // a drift outside the window is worth another try when the window can still widen; it
+      // counts as a fallback only when no wider attempt follows
+      bool wider = false;
       if (status == kPhiShort || status == kPhiWindow) {
         const double p0 = phd.p_rej_sm;
         PhiDevice::widen(phd.p_rej_sm, 0.9);
-        if (phd.p_rej_sm > p0) return 1;   // a wider window is worth another try
-        phd.fallbacks++;
-        stats.phi_device_fallbacks++;
+        wider = phd.p_rej_sm > p0 && !last;
       }
-      return -1;
+      phi_note_handback(status, !wider);
+      return wider ? 1 : -1;
     }
     stats.phi_device_calls++;
     stats.phi_sm_device_calls++;
-    const uint8_t* pk = out + o_pick;
-    for (int64_t q = 0; q < items; ++q) cen[q] = (uint8_t)(pk[q] + 1);
-    std::memcpy(sig, out + o_sig, (size_t)items * 8);
-    adopt_after_phi(*W, target, phd.fast_out(out) ? (const uint32_t*)(out + phi_state_off(T, d)) : nullptr);
+    phi_copy_params(res, T, d, nullptr, cen, sig);
+    adopt_after_phi(*W, target, phd.fast_out(out) ? res.state_words() : nullptr);
     rng_sync();                        // split-merge draws on the host next
     PhiDevice::adapt(phd.p_rej_sm, cons - 3 * items, items, 0.9);
     return kOk;
@@ -4883,30 +4810,25 @@ struct Ctx {
     const bool use_dspec = nidx == 0 && dspec.ran && dspec.lv == labels_version && dspec.moves == 0 &&
                            dspec.pos == rng.pos && dspec.epoch == rng.epoch && K == dspec.K && dspec_on();
     if (pre.active && !(use_spec && spec.moves == 0 && K == spec.K && spec.nvalid == K) && !use_dspec) pre_release();
-    const int64_t spec_fallbacks = stats.phi_device_fallbacks;
+    bool spec_handback = false;        // the speculation was handed back, not yet counted
     if (use_dspec) {
       mark("dspec_wait");
-      if (dspec_commit() == kOk) {
+      const int st = dspec_commit();
+      if (st == kOk) {
         stats.t_host_phi_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0c).count();
         mark("dspec");
         return kOk;
       }
+      spec_handback = st == kPhiHandedBack;
       if (pre.active) pre_release();
     }
     dspec.ran = false;
-    if (!use_spec) {
-      // the update on the device (csrc/phi.hip); -1: not applicable here, the host runs it
-      const bool spec_counted = stats.phi_device_fallbacks > spec_fallbacks;
-      const int64_t counted = stats.phi_device_calls + stats.phi_device_fallbacks;
-      const int st = device_update_phi(mask, nidx);
-      // one update, one count: a speculation that did not complete (dspec_commit counted a
-      // hand-back, its status stays in the mask) gives way to the outcome of this re-run
-      if (spec_counted && stats.phi_device_calls + stats.phi_device_fallbacks > counted) {
-        phd.fallbacks--;
-        stats.phi_device_fallbacks--;
-      }
-      if (st >= 0) return st;
-    }
+    // the update on the device (csrc/phi.hip); negative: the host runs it
+    const int dev = use_spec ? -1 : device_update_phi(mask, nidx);
+    if (dev >= 0) return dev;
+    // one update, one count: a speculation's hand-back (its status stays in the mask) gives way
+    // to the outcome of its re-run on the device, and is counted here when nothing ran again
+    if (spec_handback && dev != kPhiHandedBack) stats.phi_device_fallbacks++;
     int t0 = 0;
     if (use_spec && spec.moves == 0 && K == spec.K) {
       // nothing moved: the frequency tables are the pre-sweep ones (the sweep's copy-out,

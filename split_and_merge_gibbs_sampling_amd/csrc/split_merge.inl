@@ -487,9 +487,8 @@ static int sm_chain(Ctx* c, SmWork& W, const std::vector<int>& S, HState& s, int
   const int Gw = sm_wide_on() ? sm_scan_wide_grid(nS) : 0;
   const size_t wstride = 4 + 2 * (size_t)std::max(Gw, 1);
   const size_t stage_b = align16(upload_layout(1, c->dp, d, c->bw).bytes);
-  size_t o_pick, o_sig, o_ll, obytes;
-  Ctx::phi_out_layout(1, d, &o_pick, &o_sig, &o_ll, &obytes);
-  const size_t o_state = align16(obytes), out_b = align16(o_state + 625 * 4 + 64);
+  const PhiOutLayout L = phi_out_layout(1, d);
+  const size_t out_b = align16(L.o_state + 625 * 4 + 64);
   const int nu = 2 * t;                             // updates: scan k's are 2k (lower label), 2k + 1
   const int tc = std::max(t, 16);                   // (sized once for the usual t: no reallocation)
   W.d_links.ensure(tc);
@@ -614,11 +613,11 @@ static int sm_chain(Ctx* c, SmWork& W, const std::vector<int>& S, HState& s, int
       pa.sig_dev = W.d_sig.p + ((size_t)(k + 1) * 2 + e) * d;
       uint8_t* ho = W.h_cout.p + out_b * u;
       ((volatile int*)ho)[0] = -1;
-      pa.pick = ho + o_pick;
-      pa.sig_out = (double*)(ho + o_sig);
-      pa.ll = (double*)(ho + o_ll);
+      pa.pick = ho + L.o_pick;
+      pa.sig_out = (double*)(ho + L.o_sig);
+      pa.ll = (double*)(ho + L.o_ll);
       pa.status_host = (int*)ho;
-      pa.state_host = (uint32_t*)(ho + o_state);
+      pa.state_host = (uint32_t*)(ho + L.o_state);
       pa.state_host[624] = 0;
       if (++phd.gen >= (1 << 26)) {                 // generations only grow: restart from 1
         HIPCHK(hipStreamSynchronize(st));
@@ -632,7 +631,6 @@ static int sm_chain(Ctx* c, SmWork& W, const std::vector<int>& S, HState& s, int
       pa.lzz = nullptr;
       pa.tdbg = nullptr;
       HIPCHK(launch_phi2(pa, st, nullptr));
-      phd.fast_calls++;
       c->stats.phi_fast_calls++;
     }
   }
@@ -668,11 +666,11 @@ static int sm_chain(Ctx* c, SmWork& W, const std::vector<int>& S, HState& s, int
   c->mark("sm.chain_done");
   const PhiChain* cw = (const PhiChain*)(W.h_cback.p + o_cw);
   const uint32_t* hF = (const uint32_t*)W.h_cback.p;
-  auto ustat = [&](int u) { return ((const int*)(W.h_cout.p + out_b * u))[0]; };
+  auto uout = [&](int u) { return PhiOutView(W.h_cout.p + out_b * u, L); };
   // the first update that did not complete (nu: none)
   int uf = nu;
   for (int u = 0; u < nu; ++u)
-    if (ustat(u) != kPhiOk || cw[upd_w(u)].ok != 1) {
+    if (uout(u).status() != kPhiOk || cw[upd_w(u)].ok != 1) {
       uf = u;
       break;
     }
@@ -700,20 +698,11 @@ static int sm_chain(Ctx* c, SmWork& W, const std::vector<int>& S, HState& s, int
     s.counts[c2] = F2.nn;
   }
   // the parameters of the updates that completed (each cluster's last)
-  for (int u = 0; u < uf; ++u) {
-    int64_t cons = 0;
-    std::memcpy(&cons, W.h_cout.p + out_b * u + 8, 8);
-    Ctx::PhiDevice::adapt(phd.p_rej_sm, cons - 3 * (int64_t)d, d, 0.9);
-  }
+  for (int u = 0; u < uf; ++u) Ctx::PhiDevice::adapt(phd.p_rej_sm, uout(u).cons() - 3 * (int64_t)d, d, 0.9);
   for (int e = 0; e < 2; ++e) {
     int u = uf - 1;
     while (u >= 0 && (u & 1) != e) --u;
-    if (u < 0) continue;
-    const uint8_t* ho = W.h_cout.p + out_b * u;
-    const uint8_t* pk = ho + o_pick;
-    const int k = klab[e];
-    for (int j = 0; j < d; ++j) s.center[(size_t)k * d + j] = (uint8_t)(pk[j] + 1);
-    std::memcpy(&s.sigma[(size_t)k * d], ho + o_sig, (size_t)d * 8);
+    if (u >= 0) phi_copy_params(uout(u), 1, d, &klab[e], s.center.data(), s.sigma.data());
   }
   c->stats.phi_device_calls += uf;
   c->stats.phi_sm_device_calls += uf;
@@ -721,16 +710,15 @@ static int sm_chain(Ctx* c, SmWork& W, const std::vector<int>& S, HState& s, int
   c->stats.sm_chain_scans += ran;
   if (uf == nu) {
     // the host stream after the last update's draws (its state came back with its outputs)
-    const uint8_t* ho = W.h_cout.p + out_b * (nu - 1);
-    c->adopt_after_phi(*Wn, (uint64_t)cw[upd_w(nu - 1)].end, (const uint32_t*)(ho + o_state));
+    c->adopt_after_phi(*Wn, (uint64_t)cw[upd_w(nu - 1)].end, uout(nu - 1).state_words());
     *next_iter = t;
     return kOk;
   }
   // continue on the host from the first unfinished step
   c->stats.sm_chain_resumes++;
-  const int stk = ustat(uf);
+  const int stk = uout(uf).status();
   if (scan_kf && stk != kPhiOff && stk != kPhiOk) {
-    c->stats.phi_fallback_status_mask |= (int64_t)1 << std::min(std::max(stk, 0), 14);
+    c->phi_note_handback(stk, false);                // (the host's update that follows counts)
     c->stats.phi_fast_handbacks++;
     if (stk == kPhiShort || stk == kPhiWindow) Ctx::PhiDevice::widen(phd.p_rej_sm, 0.9);
   }
