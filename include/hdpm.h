@@ -140,6 +140,10 @@ typedef struct {
      * pipe_early == pipe_early_ran + pipe_early_off.  HDPM_PIPE_EARLY=0 in the environment
      * (read once per process) leaves every go to the sweep's end, for A/B runs. */
     int64_t pipe_early, pipe_early_ran, pipe_early_off;
+    /* rounds of sweeps enqueued ahead whose end the host took from the control block's sequence
+     * word (ResolveCtl::seq) instead of an event behind the resolver.  HDPM_RES_WORD=0 in the
+     * environment (read once per process) keeps the event. */
+    int64_t resolved_by_word;
 } hdpm_stats;
 
 int         hdpm_device_count(void);

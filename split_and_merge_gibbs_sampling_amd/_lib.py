@@ -84,7 +84,8 @@ class Stats(C.Structure):
                                   "labels_mirrored", "labels_downloaded", "phi_state_direct",
                                   "phi_chain_launched", "phi_chain_used", "phi_chain_dropped",
                                   "pipe_auto", "pipe_desync", "sm_chain_runs", "sm_chain_scans",
-                                  "sm_chain_resumes", "pipe_early", "pipe_early_ran", "pipe_early_off")]
+                                  "sm_chain_resumes", "pipe_early", "pipe_early_ran", "pipe_early_off",
+                                  "resolved_by_word")]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}

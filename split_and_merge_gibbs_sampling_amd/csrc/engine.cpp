@@ -8,6 +8,7 @@
 
 #include <algorithm>
 #include <cctype>
+#include <climits>
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
@@ -66,7 +67,7 @@ hipError_t launch_scatter_clusters(const uint8_t* stage, int nent, int dp, int d
                                    const double* logn = nullptr, int* zero = nullptr, int* wide_ctr = nullptr);
 hipError_t launch_phi_locate(const PipeArgs& a, hipStream_t s);
 hipError_t launch_pipe_wait(PipeSlot* slot, const ResolveCtl* prev, ResolveCtl* own, int n, PipeGate* g,
-                            long long limit, hipStream_t s, const PipeAuto& au);
+                            long long limit, hipStream_t s, const PipeAuto& au, int seq);
 hipError_t launch_pipe_check(const PipeArgs& a, hipStream_t s);
 hipError_t launch_pool_heads(const double* tab, const uint64_t* bnd, int64_t P, int d, int wb, int Ws, int bw, int ha,
                              int hb, uint64_t* head, hipStream_t s);
@@ -915,6 +916,52 @@ struct Ctx {
   hipEvent_t ev_res[2] = {nullptr, nullptr};
   size_t ctl_stride() const { return kCtlInts + 3 * (size_t)scap; }
   ResolveCtl* ctl_at(int q) { return reinterpret_cast<ResolveCtl*>(h_ctl.p + (size_t)q * ctl_stride()); }
+  // A round enqueued ahead (pre_enqueue) is waited for by its control block's sequence word
+  // (ResolveCtl::seq, wait_resolved), not by an event: the record behind its resolver left the
+  // queue idle for ~6 us before the next sweep's wait kernel.  Every launch gets the next number,
+  // so a block never sees one twice; res_seq[q] is the word the host waits for in block q, 0
+  // where the round's end is ev_res[q].  HDPM_RES_WORD=0 (read once): events for every round.
+  int round_seq = 0, pipe_seq = 0;
+  int res_seq[2] = {0, 0};
+  int next_seq() {
+    round_seq = round_seq == INT_MAX ? 1 : round_seq + 1;
+    return round_seq;
+  }
+  static bool res_word_on() {
+    static const bool on = [] {
+      const char* e = std::getenv("HDPM_RES_WORD");
+      return !(e && e[0] == '0');
+    }();
+    return on;
+  }
+  // The host's wait for the round of control block q.  By the word: a spin on ResolveCtl::seq
+  // (the block and the summary behind it are final when it holds the round's number); past the
+  // wait kernel's own limit and a margin, the stream's end decides, and a word still wrong then
+  // means the round never ran to its end: the chain state is no longer defined (false).
+  // Only the control block and the summary are read off this wait.  Everything else the resolver
+  // wrote is in device memory and is next read by kernels and copies on the same stream, which
+  // run behind it in stream order whether or not the host has waited: no new ordering is needed.
+  bool wait_resolved(int q) {
+    const int want = res_seq[q];
+    if (!want) {
+      if (ev_res[q]) HIPCHK(hipEventSynchronize(ev_res[q]));
+      else HIPCHK(hipStreamSynchronize(stream));
+      return true;
+    }
+    const int* w = &ctl_at(q)->seq;
+    const auto t0 = std::chrono::steady_clock::now();
+    const auto limit = std::chrono::microseconds((long long)((double)pipe_limit_ticks * 0.01) + 1000000);
+    for (int polls = 0;; ++polls) {
+      if (__atomic_load_n(w, __ATOMIC_ACQUIRE) == want) return true;
+      HostPool::spin_pause();
+      if ((polls & 1023) == 1023 && std::chrono::steady_clock::now() - t0 > limit) break;
+    }
+    HIPCHK(hipStreamSynchronize(stream));
+    if (__atomic_load_n(w, __ATOMIC_ACQUIRE) == want) return true;
+    have_state = false;
+    err = "a sweep enqueued ahead ended without publishing its control block";
+    return false;
+  }
   // The next sweep enqueued before this iteration's update is joined (pre_enqueue): its
   // kernels wait on the device (k_pipe_wait) for the host's go (pipe_go) or abort
   // (pre_release); slots in host-coherent memory, gates on the device.
@@ -1607,10 +1654,9 @@ struct Ctx {
     }
     stage_fill = f;
     if (stage_pipe_busy[f]) {
-      // (not yet seen resolved by the host: ev_res[q] is still that round's record)
+      // (not yet seen resolved by the host: block q's word or event is still that round's)
       const int q = stage_pipe_busy[f] - 1;
-      if (ev_res[q]) HIPCHK(hipEventSynchronize(ev_res[q]));
-      else HIPCHK(hipStreamSynchronize(stream));
+      (void)wait_resolved(q);            // (false: have_state is off, the caller's next step fails)
       stage_pipe_busy[f] = 0;
     }
     hipEvent_t& ev = ev_stage_buf[stage_fill];
@@ -2332,7 +2378,10 @@ struct Ctx {
     const bool dense_list = dense_fits && el >= kDenseMinPoints && 2 * (int64_t)el >= (int64_t)(n - p) &&
                             !(debug & 1) && dense_list_on();
     // the resolver writes its control block and summary straight into host memory
-    if (h_ctl.n < 2 * ctl_stride()) h_ctl.ensure(2 * ctl_stride(), hipHostMallocCoherent);
+    if (h_ctl.n < 2 * ctl_stride()) {
+      h_ctl.ensure(2 * ctl_stride(), hipHostMallocCoherent);
+      std::memset(h_ctl.p, 0, 2 * ctl_stride() * sizeof(int));   // (no sequence word from stale memory)
+    }
     for (auto& e : ev_res)
       if (!e) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     // HIP events between kernels cost a dispatch gap each: the prepass is timed on every
@@ -2539,10 +2588,14 @@ struct Ctx {
       HIPCHK(warm_launch_kernels(pa, ra, d_warm.p, d_warm.p + 16, stream));
       kernels_warm = true;
     }
+    // the round's end for the host: the sequence word for a round enqueued ahead, else the event
+    ra.seq = pg ? pipe_seq : next_seq();
+    const bool by_word = pg && res_word_on();
     HIPCHK(launch_resolve(ra, stream));
     mark("r.resolve");
     if (fine) HIPCHK(hipEventRecord(ev[2], stream));
-    HIPCHK(hipEventRecord(ev_res[cpar], stream));
+    res_seq[cpar] = by_word ? ra.seq : 0;
+    if (!by_word) HIPCHK(hipEventRecord(ev_res[cpar], stream));
     return kOk;
   }
 
@@ -2716,7 +2769,11 @@ struct Ctx {
       au = PipeAuto{dspec.chain, w.raw.p, (int64_t)w.start_pos, w.count, (int64_t)n * (m + 1), 1};
     }
     if (dev) HIPCHK(hipStreamWaitEvent(stream, dspec.ev, 0));   // (the update's tables, below)
-    HIPCHK(launch_pipe_wait(&h_pipe.p[q], ctl_at(par), ctl_at(q), n, &d_pipe.p[q], pipe_limit_ticks, stream, au));
+    // the round's sequence number: published by its resolver, or by the wait kernel when it
+    // gates the round off (wait_resolved)
+    pipe_seq = next_seq();
+    HIPCHK(launch_pipe_wait(&h_pipe.p[q], ctl_at(par), ctl_at(q), n, &d_pipe.p[q], pipe_limit_ticks, stream, au,
+                            pipe_seq));
     pre.au = au.on != 0;
     pre.t_enq = std::chrono::steady_clock::now();   // the kernel's clock starts no earlier
     pre.active = true;
@@ -3031,7 +3088,9 @@ struct Ctx {
         if (enqueued) pipe_early_go(m, track, freq_before_ok);
       }
       mark("prefill");
-      HIPCHK(hipEventSynchronize(ev_res[par]));
+      const bool by_word = res_seq[par] != 0;
+      if (!wait_resolved(par)) return kArg;
+      if (by_word) stats.resolved_by_word++;
       mark("resolved");
       for (int& b : stage_pipe_busy)
         if (b == par + 1) b = 0;           // this round's scatter is done with its staging buffer
@@ -3039,6 +3098,9 @@ struct Ctx {
       if (piped_round ? pre_timed[par] : round_timed) {
         float t1 = 0;
         if (piped_round) round_points = n;
+        // (the word says the resolver has ended, not that the runtime has seen the prepass's
+        // timing records complete: they precede it on the stream, so this returns at once)
+        if (by_word) HIPCHK(hipEventSynchronize(ev_pp[par][1]));
         HIPCHK(hipEventElapsedTime(&t1, piped_round ? ev_pp[par][0] : ev[0], piped_round ? ev_pp[par][1] : ev[1]));
         stats.t_prepass_ms += t1;
         stats.prepass_timed++;

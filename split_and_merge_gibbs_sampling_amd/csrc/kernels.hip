@@ -2061,6 +2061,13 @@ __device__ __forceinline__ void resolve_init(const ResolveArgs& a, const RState&
   __syncthreads();
 }
 
+// The writer of a control block (a resolver's lane 0, or k_pipe_wait for a sweep it gates
+// off), after the block's other fields: they are in host memory before the word is.
+__device__ __forceinline__ void publish_seq(ResolveCtl* c, int seq) {
+  __threadfence_system();
+  __hip_atomic_store(&c->seq, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
 // all threads: write the state back, the host summary and the control block
 __device__ __forceinline__ void resolve_finish(const ResolveArgs& a, const RState& st, int nlog, const long long* tp,
                                                bool prof) {
@@ -2078,6 +2085,11 @@ __device__ __forceinline__ void resolve_finish(const ResolveArgs& a, const RStat
     a.summary[scap + s] = s < S.nslots ? st.cnt[s] : 0;
     a.summary[2 * scap + s] = s < S.nslots ? a.slot_src[s] : -1;
   }
+  // the summary is complete in host memory before the control block's sequence word says so
+  // (a host that waits for the word, not for the kernel's end: engine.cpp wait_resolved); every
+  // wave releases its own stores, then the barrier
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
+  __syncthreads();
   if (wv != 0) return;
   if (prof && lane == 0) {
     for (int k = 0; k < 7; ++k) a.prof[k] = tp[k];
@@ -2086,13 +2098,15 @@ __device__ __forceinline__ void resolve_finish(const ResolveArgs& a, const RStat
   }
   if (lane == 0 && a.mcount) *a.mcount = nlog;
   if (lane == 0) {
-    ResolveCtl c;
-    c.next = S.next; c.status = S.status; c.restart = S.restart; c.K = S.K; c.nslots = S.nslots;
-    c.moves = S.moves; c.exact = S.exact; c.checked = S.checked;
-    c.listed = *a.dense_total;
-    c.aborted = S.aborted;
-    c.uncertain = a.uncertain ? *a.uncertain : -1;
-    *a.ctl = c;
+    // every field but seq, then seq alone behind a system-scope fence: the block is final
+    // when the host reads the launch's sequence number there
+    ResolveCtl* c = a.ctl;
+    c->next = S.next; c->status = S.status; c->restart = S.restart; c->K = S.K; c->nslots = S.nslots;
+    c->moves = S.moves; c->exact = S.exact; c->checked = S.checked;
+    c->listed = *a.dense_total;
+    c->aborted = S.aborted;
+    c->uncertain = a.uncertain ? *a.uncertain : -1;
+    publish_seq(c, a.seq);
   }
 }
 
@@ -4348,7 +4362,7 @@ hipError_t launch_finish_sweep(int* counts, int* sol, int* los, int* src, int ca
 // kernels: go, and the previous sweep's control block (written by its resolver before this
 // kernel in stream order) shows it complete without a move.
 __global__ void k_pipe_wait(PipeSlot* slot, const ResolveCtl* prev, ResolveCtl* own, int n, PipeGate* g,
-                            long long limit, PipeAuto au) {
+                            long long limit, PipeAuto au, int seq) {
   if (threadIdx.x != 0) return;
   if (au.on) {
     // the device's own go (PipeAuto): the update's chain word, the previous sweep's control block
@@ -4402,6 +4416,9 @@ __global__ void k_pipe_wait(PipeSlot* slot, const ResolveCtl* prev, ResolveCtl* 
     o->next = 0;
     o->aborted = 0;
     o->uncertain = -1;
+    // its resolver returns at the gate: the block's sequence word, which the host may wait for
+    // in place of that kernel's end, is published here
+    publish_seq(own, seq);
   }
   // the decision, for a host that gave its go before it knew the previous sweep's outcome (the
   // early go, engine.cpp pipe_early_go): 1 went, 2 declined.  (With PipeAuto the word already
@@ -4409,8 +4426,8 @@ __global__ void k_pipe_wait(PipeSlot* slot, const ResolveCtl* prev, ResolveCtl* 
   if (!au.on) __hip_atomic_store(&slot->dev, ok ? 1 : 2, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 hipError_t launch_pipe_wait(PipeSlot* slot, const ResolveCtl* prev, ResolveCtl* own, int n, PipeGate* g,
-                            long long limit, hipStream_t s, const PipeAuto& au) {
-  HDPM_LAUNCH(k_pipe_wait, dim3(1), dim3(64), 0, s, slot, prev, own, n, g, limit, au);
+                            long long limit, hipStream_t s, const PipeAuto& au, int seq) {
+  HDPM_LAUNCH(k_pipe_wait, dim3(1), dim3(64), 0, s, slot, prev, own, n, g, limit, au, seq);
   return hipGetLastError();
 }
 

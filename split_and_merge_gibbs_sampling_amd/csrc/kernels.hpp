@@ -264,7 +264,11 @@ struct ResolveCtl {
                   // the state is consistent at `next` (restart there, with k_resolve_fp)
   int uncertain;  // dense launches: listed points the prepass's margin test would have listed
                   // (k_snap_draws' count), or -1
+  int seq;        // the launch's sequence number (ResolveArgs::seq), stored last and alone: a host
+                  // that reads it here reads the final block and summary (publish_seq)
 };
+// (12 ints of the 16 a block takes in host memory: engine.cpp kCtlInts and its static_assert)
+static_assert(sizeof(ResolveCtl) == 12 * sizeof(int), "control block layout");
 
 struct ResolveArgs {
   int n, d, dp, m;
@@ -329,6 +333,7 @@ struct ResolveArgs {
   int all_listed;            // 1: every point of [p0, n) listed (k_dense_list): nothing to re-test
   long long fpg_limit;       // a grid barrier gives up after this many wall_clock64 ticks (100 MHz)
   int fpg_fail;              // testing: workgroup 0 gives up at its fpg_fail-th grid barrier (0: never)
+  int seq = 0;               // the launch's sequence number, published in ResolveCtl::seq at the end
 };
 // Cross-workgroup scratch of k_resolve_fpg (G workgroups), in ints: barrier [0, 96), state mirror
 // [96, 96 + 8 + 3 * 64 + 16), then per workgroup: stop and changed (two parities each), fail,
