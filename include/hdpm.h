@@ -239,6 +239,36 @@ int hdpm_record_take(hdpm_ctx* ctx, double* centers, double* sigmas, int64_t* nr
 int hdpm_rng_fill_device(hdpm_ctx* ctx, int64_t count, uint32_t* out);
 int hdpm_get_stats(const hdpm_ctx* ctx, hdpm_stats* out);
 int hdpm_reset_stats(hdpm_ctx* ctx);
+/* The addends of the last split-merge move's log acceptance ratio (code/split_merge.cpp:438-540),
+ * as the move computed them: a host-side record, filled by every move that reaches the
+ * acceptance test (sm:591) -- through hdpm_split_and_merge, hdpm_iteration* or
+ * hdpm_run_markov_chain alike -- and costing no kernel, copy or wait.  A move that returns an
+ * error leaves kind = 0.  term[] holds the fourteen function values in the reference's source
+ * order, unsigned (the signs belong to the formula).
+ *   split (sm:438-487): 0 log(alpha); 1, 2 lgamma(n) of gamma_star's c(i1), c(i2); 3, 4
+ *     priors(gamma_star, c(i1) / c(i2)); 5 lgamma(n) of gamma's c(i1); 6 priors(gamma, c(i1));
+ *     7-9 the three loglikelihood_hamming calls; 10-12 the three logprobgs_phi calls;
+ *     13 logprobgs_c_i.  size[] = the sizes under terms 1, 2, 5.
+ *     log_prior = t0 + t1 + t2 + t3 + t4 - t5 - t6, log_likelihood = t7 + t8 - t9,
+ *     log_proposal = t10 - t11 - t12 - t13.
+ *   merge (sm:489-540): 0 lgamma(n) of gamma_star's c(i1); 1 priors(gamma_star, c(i1));
+ *     2 log(alpha); 3, 4 lgamma(n) of gamma's c(i1), c(i2); 5, 6 priors(gamma, c(i1) / c(i2));
+ *     7-9 loglikelihood_hamming; 10, 11 logprobgs_phi(gamma, launch, i1 / i2); 12 logprobgs_c_i;
+ *     13 logprobgs_phi(gamma_star, merge launch, i2).  size[] = the sizes under terms 0, 3, 4.
+ *     log_prior = t0 + t1 - t2 - t3 - t4 - t5 - t6, log_likelihood = t7 - t8 - t9,
+ *     log_proposal = t10 + t11 + t12 - t13.
+ * Each partial sum starts from 0.0 and adds left to right; log_ratio = log_prior +
+ * log_likelihood + log_proposal; the move is accepted when log_u < min(0, log_ratio). */
+typedef struct {
+    int32_t kind;            /* 0: no completed move yet, 1: split (sm:438-487), 2: merge (sm:489-540) */
+    int32_t accepted, i1, i2, nS;
+    int32_t size[3];         /* the three cluster sizes whose lgamma enters, in the formula's order */
+    double  term[14];        /* the addends as the functions return them, in the reference's source order */
+    double  log_prior, log_likelihood, log_proposal;
+    double  log_ratio;       /* the sum before min(0, .) */
+    double  log_u;           /* log(unif) of sm:591 */
+} hdpm_sm_terms;
+int hdpm_sm_last_terms(const hdpm_ctx* ctx, hdpm_sm_terms* out);
 /* Testing / diagnostics.  mode bit 0: evaluate every point on the exact path (no
  * certainty shortcut); bit 1: print per-phase timings to stderr; bit 2: compute the
  * log-likelihood with the per-point kernel (no regrouping into match counts); bit 3: no

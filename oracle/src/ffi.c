@@ -235,3 +235,6 @@ int orc_ffi_split_and_merge(const double* data, int n, int d, const int* attrisi
     orc_state_free(&s);
     return st;
 }
+
+/* the last completed split-merge move's acceptance addends (oracle.h orc_sm_terms) */
+void orc_ffi_sm_last_terms(orc_sm_terms* out) { *out = *orc_sm_last_terms(); }

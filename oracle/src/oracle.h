@@ -136,6 +136,20 @@ double orc_logprobgs_c_i(const orc_state* gs, const orc_state* g, const orc_aux*
 int orc_split_and_merge(orc_state* s, const orc_aux* A, int t, int r, int idx_1_sm,
                         orc_rng* rng, int fast, int* accepted);                   /* sm:542-598 */
 
+/* The addends of the last move's log acceptance ratio (sm:438-540): the layout, term order and
+ * meaning of include/hdpm.h's hdpm_sm_terms.  Filled by split_acc_prob / merge_acc_prob and
+ * completed by orc_split_and_merge; a move that returns an error leaves kind = 0. */
+typedef struct {
+    int32_t kind;            /* 0: no completed move yet, 1: split, 2: merge */
+    int32_t accepted, i1, i2, nS;
+    int32_t size[3];
+    double  term[14];
+    double  log_prior, log_likelihood, log_proposal;
+    double  log_ratio;
+    double  log_u;
+} orc_sm_terms;
+const orc_sm_terms* orc_sm_last_terms(void);
+
 /* ---- flat entry points for ctypes (tests / bench cpu_baseline) ---- */
 typedef struct {
     int verbose, m, iterations, L, burnin, t, r;

@@ -202,27 +202,40 @@ static double priors(const orc_state* s, int c, const orc_aux* A, int* err) {
 
 static double min0(double x) { return (x < 0.0) ? x : 0.0; }   /* std::min(0.0, x) */
 
+/* the move in progress (g_rec) and the last completed one (g_last), oracle.h orc_sm_terms */
+static orc_sm_terms g_rec, g_last;
+const orc_sm_terms* orc_sm_last_terms(void) { return &g_last; }
+
 /* sm:438-487 split_acc_prob */
 static double split_acc_prob(const orc_state* sp, const orc_state* st, const orc_state* sl,
                              const orc_state* ml, const int* S, int nS, int i1, int i2,
                              const orc_aux* A, int* err) {
     double alpha = A->gamma;
     double log_prior = 0.0, log_likelihood = 0.0, log_proposal = 0.0;
-    log_prior += log(alpha);
-    log_prior += lgamma((double)count_eq(sp->c_i, A->n, sp->c_i[i1]));
-    log_prior += lgamma((double)count_eq(sp->c_i, A->n, sp->c_i[i2]));
-    log_prior += priors(sp, sp->c_i[i1], A, err);
-    log_prior += priors(sp, sp->c_i[i2], A, err);
-    log_prior -= lgamma((double)count_eq(st->c_i, A->n, st->c_i[i1]));
-    log_prior -= priors(st, st->c_i[i1], A, err);
-    log_likelihood += loglikelihood_hamming(sp, sp->c_i[i1], A);
-    log_likelihood += loglikelihood_hamming(sp, sp->c_i[i2], A);
-    log_likelihood -= loglikelihood_hamming(st, st->c_i[i1], A);
-    log_proposal += logprobgs_phi(st, ml, A, i1, err);
-    log_proposal -= logprobgs_phi(sp, sl, A, i1, err);
-    log_proposal -= logprobgs_phi(sp, sl, A, i2, err);
-    log_proposal -= orc_logprobgs_c_i(sp, sl, A, S, nS, i1, i2);
-    return min0(log_prior + log_likelihood + log_proposal);
+    orc_sm_terms* R = &g_rec;
+    double* tv = R->term;
+    memset(R, 0, sizeof *R);
+    R->kind = 1;
+    R->size[0] = count_eq(sp->c_i, A->n, sp->c_i[i1]);
+    R->size[1] = count_eq(sp->c_i, A->n, sp->c_i[i2]);
+    R->size[2] = count_eq(st->c_i, A->n, st->c_i[i1]);
+    log_prior += (tv[0] = log(alpha));
+    log_prior += (tv[1] = lgamma((double)R->size[0]));
+    log_prior += (tv[2] = lgamma((double)R->size[1]));
+    log_prior += (tv[3] = priors(sp, sp->c_i[i1], A, err));
+    log_prior += (tv[4] = priors(sp, sp->c_i[i2], A, err));
+    log_prior -= (tv[5] = lgamma((double)R->size[2]));
+    log_prior -= (tv[6] = priors(st, st->c_i[i1], A, err));
+    log_likelihood += (tv[7] = loglikelihood_hamming(sp, sp->c_i[i1], A));
+    log_likelihood += (tv[8] = loglikelihood_hamming(sp, sp->c_i[i2], A));
+    log_likelihood -= (tv[9] = loglikelihood_hamming(st, st->c_i[i1], A));
+    log_proposal += (tv[10] = logprobgs_phi(st, ml, A, i1, err));
+    log_proposal -= (tv[11] = logprobgs_phi(sp, sl, A, i1, err));
+    log_proposal -= (tv[12] = logprobgs_phi(sp, sl, A, i2, err));
+    log_proposal -= (tv[13] = orc_logprobgs_c_i(sp, sl, A, S, nS, i1, i2));
+    R->log_prior = log_prior; R->log_likelihood = log_likelihood; R->log_proposal = log_proposal;
+    R->log_ratio = log_prior + log_likelihood + log_proposal;
+    return min0(R->log_ratio);
 }
 
 /* sm:489-540 merge_acc_prob */
@@ -231,21 +244,30 @@ static double merge_acc_prob(const orc_state* sm, const orc_state* st, const orc
                              const orc_aux* A, int* err) {
     double alpha = A->gamma;
     double log_prior = 0.0, log_likelihood = 0.0, log_proposal = 0.0;
-    log_prior += lgamma((double)count_eq(sm->c_i, A->n, sm->c_i[i1]));
-    log_prior += priors(sm, sm->c_i[i1], A, err);
-    log_prior -= log(alpha);
-    log_prior -= lgamma((double)count_eq(st->c_i, A->n, st->c_i[i1]));
-    log_prior -= lgamma((double)count_eq(st->c_i, A->n, st->c_i[i2]));
-    log_prior -= priors(st, st->c_i[i1], A, err);
-    log_prior -= priors(st, st->c_i[i2], A, err);
-    log_likelihood += loglikelihood_hamming(sm, sm->c_i[i2], A);
-    log_likelihood -= loglikelihood_hamming(st, st->c_i[i1], A);
-    log_likelihood -= loglikelihood_hamming(st, st->c_i[i2], A);
-    log_proposal += logprobgs_phi(st, sl, A, i1, err);
-    log_proposal += logprobgs_phi(st, sl, A, i2, err);
-    log_proposal += orc_logprobgs_c_i(st, sl, A, S, nS, i1, i2);
-    log_proposal -= logprobgs_phi(sm, ml, A, i2, err);
-    return min0(log_prior + log_likelihood + log_proposal);
+    orc_sm_terms* R = &g_rec;
+    double* tv = R->term;
+    memset(R, 0, sizeof *R);
+    R->kind = 2;
+    R->size[0] = count_eq(sm->c_i, A->n, sm->c_i[i1]);
+    R->size[1] = count_eq(st->c_i, A->n, st->c_i[i1]);
+    R->size[2] = count_eq(st->c_i, A->n, st->c_i[i2]);
+    log_prior += (tv[0] = lgamma((double)R->size[0]));
+    log_prior += (tv[1] = priors(sm, sm->c_i[i1], A, err));
+    log_prior -= (tv[2] = log(alpha));
+    log_prior -= (tv[3] = lgamma((double)R->size[1]));
+    log_prior -= (tv[4] = lgamma((double)R->size[2]));
+    log_prior -= (tv[5] = priors(st, st->c_i[i1], A, err));
+    log_prior -= (tv[6] = priors(st, st->c_i[i2], A, err));
+    log_likelihood += (tv[7] = loglikelihood_hamming(sm, sm->c_i[i2], A));
+    log_likelihood -= (tv[8] = loglikelihood_hamming(st, st->c_i[i1], A));
+    log_likelihood -= (tv[9] = loglikelihood_hamming(st, st->c_i[i2], A));
+    log_proposal += (tv[10] = logprobgs_phi(st, sl, A, i1, err));
+    log_proposal += (tv[11] = logprobgs_phi(st, sl, A, i2, err));
+    log_proposal += (tv[12] = orc_logprobgs_c_i(st, sl, A, S, nS, i1, i2));
+    log_proposal -= (tv[13] = logprobgs_phi(sm, ml, A, i2, err));
+    R->log_prior = log_prior; R->log_likelihood = log_likelihood; R->log_proposal = log_proposal;
+    R->log_ratio = log_prior + log_likelihood + log_proposal;
+    return min0(R->log_ratio);
 }
 
 /* sm:303-352 split_launch_state */
@@ -314,6 +336,7 @@ int orc_split_and_merge(orc_state* s, const orc_aux* A, int t, int rr, int idx_1
     (void)i1;
     *accepted = 0;
     g_tables = fast >= 2;
+    memset(&g_last, 0, sizeof g_last);     /* (a move that returns an error leaves kind 0) */
     /* sample(seq(0, n-1), 2, FALSE): EmpiricalSample without replacement */
     {
         int nn = n;
@@ -357,11 +380,17 @@ int orc_split_and_merge(orc_state* s, const orc_aux* A, int t, int rr, int idx_1
     if (gerr) { e = gerr; goto out; }
     e = orc_validate_state(&ss);
     if (e) goto out;
-    if (log(orc_unif_rand(rng)) < acpt) {
+    g_rec.i1 = i1; g_rec.i2 = i2; g_rec.nS = nS;
+    g_rec.log_u = log(orc_unif_rand(rng));
+    if (g_rec.log_u < acpt) {
         e = orc_clean_var(s, &ss, A);
         if (e) goto out;
         e = orc_validate_state(s);
         *accepted = 1;
+    }
+    if (!e) {
+        g_rec.accepted = *accepted;
+        g_last = g_rec;
     }
 out:
     orc_state_free(&sl); orc_state_free(&ml); orc_state_free(&ss);

@@ -30,7 +30,7 @@ EXPORTS = (
     "hdpm_psm_build", "hdpm_psm_rows", "hdpm_psm_vi_lb",
     "hdpm_trace_build", "hdpm_trace_terms", "hdpm_trace_losses", "hdpm_trace_tables",
     "hdpm_trace_groups", "hdpm_trace_group_info", "hdpm_trace_avg_tree", "hdpm_trace_cut_losses",
-    "hdpm_trace_cut_labels", "hdpm_trace_distances", "hdpm_trace_affinity",
+    "hdpm_trace_cut_labels", "hdpm_trace_distances", "hdpm_trace_affinity", "hdpm_sm_last_terms",
 )
 
 OPT_HIG_LOGSPACE = 1
@@ -91,6 +91,20 @@ class Stats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class SmTerms(C.Structure):
+    """hdpm_sm_terms (include/hdpm.h)."""
+    _fields_ = [("kind", C.c_int32), ("accepted", C.c_int32), ("i1", C.c_int32), ("i2", C.c_int32),
+                ("nS", C.c_int32), ("size", C.c_int32 * 3), ("term", C.c_double * 14),
+                ("log_prior", C.c_double), ("log_likelihood", C.c_double), ("log_proposal", C.c_double),
+                ("log_ratio", C.c_double), ("log_u", C.c_double)]
+
+    def as_dict(self):
+        return {"kind": self.kind, "accepted": self.accepted, "i1": self.i1, "i2": self.i2, "nS": self.nS,
+                "size": list(self.size), "term": list(self.term), "log_prior": self.log_prior,
+                "log_likelihood": self.log_likelihood, "log_proposal": self.log_proposal,
+                "log_ratio": self.log_ratio, "log_u": self.log_u}
+
+
 def build(force: bool = False) -> str:
     """Compile the HIP kernels + host runtime for gfx950 into LIB_PATH (hipcc)."""
     srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC)]
@@ -136,6 +150,7 @@ def lib():
         "hdpm_split_and_merge": ([vp, i32, i32, i32, P(i32)], C.c_int),
         "hdpm_run_markov_chain": ([vp, P(ChainParams), vp, vp, vp, vp, vp, vp, vp], C.c_int),
         "hdpm_get_stats": ([vp, P(Stats)], C.c_int),
+        "hdpm_sm_last_terms": ([vp, P(SmTerms)], C.c_int),
         "hdpm_init_chain": ([vp, P(ChainParams), vp], C.c_int),
         "hdpm_iteration": ([vp, P(ChainParams), i32, P(i32), P(i32), P(f64)], C.c_int),
         "hdpm_iterations": ([vp, P(ChainParams), i32, i32, P(i32), vp, vp], C.c_int),

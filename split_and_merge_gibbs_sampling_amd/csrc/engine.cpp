@@ -1074,6 +1074,7 @@ struct Ctx {
   PinBuf<double> h_partial;
 
   hdpm_stats stats{};
+  hdpm_sm_terms sm_terms{};           // the last split-merge move's acceptance addends (kind 0: none)
   int64_t launch_count = 0;           // resolver launches issued (prepass timing cadence)
   bool round_timed = false, round_fine = false;
   int64_t round_points = 0;
@@ -5644,6 +5645,12 @@ int hdpm_get_stats(const hdpm_ctx* h, hdpm_stats* out) {
   auto* ctx = reinterpret_cast<const Ctx*>(h);
   if (!ctx || !out) return HDPM_E_ARG;
   *out = ctx->stats;
+  return HDPM_OK;
+}
+int hdpm_sm_last_terms(const hdpm_ctx* h, hdpm_sm_terms* out) {
+  auto* ctx = reinterpret_cast<const Ctx*>(h);
+  if (!ctx || !out) return HDPM_E_ARG;
+  *out = ctx->sm_terms;
   return HDPM_OK;
 }
 // Counters and synchronisation leave a prepared sweep in place (they change no chain

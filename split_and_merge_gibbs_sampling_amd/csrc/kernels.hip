@@ -4986,8 +4986,18 @@ hipError_t launch_sm_scan_wide(const SmArgs& a, int G, hipStream_t s) {
   return hipGetLastError();
 }
 
+// two_sum for sums that may hold an infinite addend (log(0) = -inf): there s - a is inf - inf,
+// so the error term is taken as 0 and the sum stays the infinity the plain sum gives.  Finite
+// sums are two_sum's, bit for bit.
+__device__ __forceinline__ void two_sum_inf(double a, double b, double& s, double& e) {
+  two_sum(a, b, s, e);
+  if (isinf(s)) e = 0.0;
+}
+
 // logprobgs_c_i terms: log(probs[current side]) with fixed launch sizes; compensated
-// per-block sums (hi, lo).
+// per-block sums (hi, lo).  A point whose current side has probability exactly 0 (its two
+// log-weights more than ~745 apart) contributes -inf, and the block's sum is then -inf as the
+// reference's (sm:159), not NaN.
 __global__ __launch_bounds__(kBlock) void k_sm_lpgs(SmArgs a) {
   const int q = blockIdx.x * kBlock + threadIdx.x;
   double hi = 0.0, lo = 0.0;
@@ -5008,7 +5018,7 @@ __global__ __launch_bounds__(kBlock) void k_sm_lpgs(SmArgs a) {
   for (int o = 32; o > 0; o >>= 1) {
     const double oh = __shfl_xor(hi, o), ol = __shfl_xor(lo, o);
     double s, e;
-    two_sum(hi, oh, s, e);
+    two_sum_inf(hi, oh, s, e);
     hi = s;
     lo = lo + ol + e;
   }
@@ -5020,7 +5030,7 @@ __global__ __launch_bounds__(kBlock) void k_sm_lpgs(SmArgs a) {
     double H = 0.0, Lo = 0.0;
     for (int w = 0; w < kBlock / kWave; ++w) {
       double s, e;
-      two_sum(H, sh[w][0], s, e);
+      two_sum_inf(H, sh[w][0], s, e);
       H = s;
       Lo += sh[w][1] + e;
     }

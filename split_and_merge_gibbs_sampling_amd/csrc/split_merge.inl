@@ -947,7 +947,10 @@ static double logprobgs_c_i(Ctx* c, const HState& gs, const HState& g, const std
   for (int b = 0; b < nb; ++b) {
     const double x = W.h_out[2 * b];
     const double s = hi + x, bb = s - hi;
-    lo += (hi - (s - bb)) + (x - bb) + W.h_out[2 * b + 1];
+    // (a block that held a log(0) term is -inf: the error term of inf - inf is left out, so the
+    // sum is the reference's -inf; finite sums are unchanged)
+    if (std::isinf(s)) lo += W.h_out[2 * b + 1];
+    else lo += (hi - (s - bb)) + (x - bb) + W.h_out[2 * b + 1];
     hi = s;
   }
   return hi + lo;
@@ -1141,6 +1144,7 @@ int Ctx::split_and_merge(int t, int r, int idx_1_sm, int* accepted) {
   if (!have_state) { err = "no state"; return kArg; }
   (void)idx_1_sm;  // overwritten by select_observations_random (sm:278), as in the reference
   *accepted = 0;
+  sm_terms = hdpm_sm_terms{};          // (a move that returns an error leaves kind 0)
   HState st;
   ctx_to_hstate(this, st);
   // every host index below is a label < K (the state's arrays are K x d): refuse a state
@@ -1220,6 +1224,8 @@ int Ctx::split_and_merge(int t, int r, int idx_1_sm, int* accepted) {
   // proposal
   HState ss;
   double acpt;
+  hdpm_sm_terms rec{};                 // the addends in source order (include/hdpm.h)
+  double* const term = rec.term;
   int gerr = kOk;
   const double alpha = gamma;
   if (st.c[i1] == st.c[i2]) {
@@ -1230,25 +1236,29 @@ int Ctx::split_and_merge(int t, int r, int idx_1_sm, int* accepted) {
     SmTimer tm(stats.t_sm_terms_ms);
     mark("sm.t0");
     double log_prior = 0.0, log_likelihood = 0.0, log_proposal = 0.0;
-    log_prior += std::log(alpha);
-    log_prior += std::lgamma((double)F1.nn);
-    log_prior += std::lgamma((double)F2.nn);
-    log_prior += priors(this, ss, ss.c[i1], &gerr);
-    log_prior += priors(this, ss, ss.c[i2], &gerr);
-    log_prior -= std::lgamma((double)FM.nn);
-    log_prior -= priors(this, st, st.c[i1], &gerr);
+    rec.kind = 1;
+    rec.size[0] = F1.nn; rec.size[1] = F2.nn; rec.size[2] = FM.nn;
+    log_prior += (term[0] = std::log(alpha));
+    log_prior += (term[1] = std::lgamma((double)F1.nn));
+    log_prior += (term[2] = std::lgamma((double)F2.nn));
+    log_prior += (term[3] = priors(this, ss, ss.c[i1], &gerr));
+    log_prior += (term[4] = priors(this, ss, ss.c[i2], &gerr));
+    log_prior -= (term[5] = std::lgamma((double)FM.nn));
+    log_prior -= (term[6] = priors(this, st, st.c[i1], &gerr));
     mark("sm.t.priors");
-    log_likelihood += loglikelihood_hamming(this, ss, ss.c[i1], F1);
-    log_likelihood += loglikelihood_hamming(this, ss, ss.c[i2], F2);
-    log_likelihood -= loglikelihood_hamming(this, st, st.c[i1], FM);
+    log_likelihood += (term[7] = loglikelihood_hamming(this, ss, ss.c[i1], F1));
+    log_likelihood += (term[8] = loglikelihood_hamming(this, ss, ss.c[i2], F2));
+    log_likelihood -= (term[9] = loglikelihood_hamming(this, st, st.c[i1], FM));
     mark("sm.t.ll");
-    log_proposal += logprobgs_phi(this, st, ml, i1, FM, &gerr);
-    log_proposal -= logprobgs_phi(this, ss, sl, i1, F1, &gerr);
-    log_proposal -= logprobgs_phi(this, ss, sl, i2, F2, &gerr);
+    log_proposal += (term[10] = logprobgs_phi(this, st, ml, i1, FM, &gerr));
+    log_proposal -= (term[11] = logprobgs_phi(this, ss, sl, i1, F1, &gerr));
+    log_proposal -= (term[12] = logprobgs_phi(this, ss, sl, i2, F2, &gerr));
     mark("sm.t.lpphi");
-    log_proposal -= logprobgs_c_i(this, ss, sl, S, i1, i2, n1_sl, n2_sl);
+    log_proposal -= (term[13] = logprobgs_c_i(this, ss, sl, S, i1, i2, n1_sl, n2_sl));
     mark("sm.t.lpci");
-    acpt = min0(log_prior + log_likelihood + log_proposal);
+    rec.log_prior = log_prior; rec.log_likelihood = log_likelihood; rec.log_proposal = log_proposal;
+    rec.log_ratio = log_prior + log_likelihood + log_proposal;
+    acpt = min0(rec.log_ratio);
   } else {
     ss = ml;
     e = hupdate_phi_pair(this, ss, ss.c[i2], FM, ss.c[i2], FM);
@@ -1274,35 +1284,43 @@ int Ctx::split_and_merge(int t, int r, int idx_1_sm, int* accepted) {
     freq_minus(FM, S1, S2);
     mark("sm.t.freq");
     double log_prior = 0.0, log_likelihood = 0.0, log_proposal = 0.0;
-    log_prior += std::lgamma((double)FM.nn);
-    log_prior += priors(this, ss, ss.c[i1], &gerr);
-    log_prior -= std::log(alpha);
-    log_prior -= std::lgamma((double)S1.nn);
-    log_prior -= std::lgamma((double)S2.nn);
-    log_prior -= priors(this, st, st.c[i1], &gerr);
-    log_prior -= priors(this, st, st.c[i2], &gerr);
+    rec.kind = 2;
+    rec.size[0] = FM.nn; rec.size[1] = S1.nn; rec.size[2] = S2.nn;
+    log_prior += (term[0] = std::lgamma((double)FM.nn));
+    log_prior += (term[1] = priors(this, ss, ss.c[i1], &gerr));
+    log_prior -= (term[2] = std::log(alpha));
+    log_prior -= (term[3] = std::lgamma((double)S1.nn));
+    log_prior -= (term[4] = std::lgamma((double)S2.nn));
+    log_prior -= (term[5] = priors(this, st, st.c[i1], &gerr));
+    log_prior -= (term[6] = priors(this, st, st.c[i2], &gerr));
     mark("sm.t.priors");
-    log_likelihood += loglikelihood_hamming(this, ss, ss.c[i2], FM);
-    log_likelihood -= loglikelihood_hamming(this, st, st.c[i1], S1);
-    log_likelihood -= loglikelihood_hamming(this, st, st.c[i2], S2);
+    log_likelihood += (term[7] = loglikelihood_hamming(this, ss, ss.c[i2], FM));
+    log_likelihood -= (term[8] = loglikelihood_hamming(this, st, st.c[i1], S1));
+    log_likelihood -= (term[9] = loglikelihood_hamming(this, st, st.c[i2], S2));
     mark("sm.t.ll");
-    log_proposal += logprobgs_phi(this, st, sl, i1, S1, &gerr);
-    log_proposal += logprobgs_phi(this, st, sl, i2, S2, &gerr);
-    log_proposal += logprobgs_c_i(this, st, sl, S, i1, i2, n1_sl, n2_sl);
-    log_proposal -= logprobgs_phi(this, ss, ml, i2, FM, &gerr);
+    log_proposal += (term[10] = logprobgs_phi(this, st, sl, i1, S1, &gerr));
+    log_proposal += (term[11] = logprobgs_phi(this, st, sl, i2, S2, &gerr));
+    log_proposal += (term[12] = logprobgs_c_i(this, st, sl, S, i1, i2, n1_sl, n2_sl));
+    log_proposal -= (term[13] = logprobgs_phi(this, ss, ml, i2, FM, &gerr));
     mark("sm.t.lp");
-    acpt = min0(log_prior + log_likelihood + log_proposal);
+    rec.log_prior = log_prior; rec.log_likelihood = log_likelihood; rec.log_proposal = log_proposal;
+    rec.log_ratio = log_prior + log_likelihood + log_proposal;
+    acpt = min0(rec.log_ratio);
   }
   if (gerr) { err = "norm_const2 - hypergeometric diverging with infinity"; return gerr; }
   e = hvalidate_counted(ss);
   if (e) { err = "State validation failed: split_and_merge - state_star"; return e; }
-  if (std::log(rng.unif()) < acpt) {   // sm:591
+  rec.i1 = i1; rec.i2 = i2; rec.nS = (int32_t)S.size();
+  rec.log_u = std::log(rng.unif());
+  if (rec.log_u < acpt) {              // sm:591
     HState ns = st;
     e = clean_var(this, ns, ss);
     if (e) { err = "State validation failed: clean_var"; return e; }
     hstate_to_ctx(this, ns);
     *accepted = 1;
   }
+  rec.accepted = *accepted;
+  sm_terms = rec;
   return kOk;
 }
 

@@ -168,6 +168,14 @@ class Engine:
         self._check(self._L.hdpm_split_and_merge(self._h, int(t), int(r), int(idx_1_sm), C.byref(acc)))
         return acc.value
 
+    def sm_last_terms(self) -> dict:
+        """The addends of the last split-merge move's log acceptance ratio (include/hdpm.h
+        hdpm_sm_terms): kind 0 (no completed move yet), 1 (split) or 2 (merge), the fourteen
+        terms in the reference's source order, the partial sums, log_ratio and log_u."""
+        t = _lib.SmTerms()
+        self._check(self._L.hdpm_sm_last_terms(self._h, C.byref(t)))
+        return t.as_dict()
+
     def stats(self) -> dict:
         s = _lib.Stats()
         self._check(self._L.hdpm_get_stats(self._h, C.byref(s)))

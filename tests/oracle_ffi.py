@@ -24,9 +24,19 @@ class ChainParams(C.Structure):
         "n8_step_size", "sam_step_size", "thinning", "fast")]
 
 
+class SmTerms(C.Structure):
+    """orc_sm_terms (oracle/src/oracle.h): the layout of include/hdpm.h's hdpm_sm_terms."""
+    _fields_ = [("kind", C.c_int32), ("accepted", C.c_int32), ("i1", C.c_int32), ("i2", C.c_int32),
+                ("nS", C.c_int32), ("size", C.c_int32 * 3), ("term", C.c_double * 14),
+                ("log_prior", C.c_double), ("log_likelihood", C.c_double), ("log_proposal", C.c_double),
+                ("log_ratio", C.c_double), ("log_u", C.c_double)]
+
+
 def build(force: bool = False) -> str:
-    if force or not os.path.exists(LIB_PATH):
-        subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "oracle")], check=True)
+    """make decides: it does nothing when liboracle.so is newer than its sources, and a library
+    left from an older tree is rebuilt instead of loaded."""
+    subprocess.run(["make", "-s"] + (["-B"] if force else []) + ["-C", os.path.join(ROOT, "oracle")],
+                   check=True)
     return LIB_PATH
 
 
@@ -82,6 +92,8 @@ def lib():
                                            _f64p, _i32p, _i32p]
         L.orc_run_markov_chain_trace.argtypes = L.orc_run_markov_chain.argtypes + [
             _i32p, _i32p, _f64p, _f64p, C.c_int64]
+        L.orc_ffi_sm_last_terms.argtypes = [C.POINTER(SmTerms)]
+        L.orc_ffi_sm_last_terms.restype = None
         _lib = L
     return _lib
 
@@ -277,6 +289,17 @@ def split_and_merge(codes, attrisize, gamma, v, w, state: OracleState, t, r, idx
                                        t, r, idx_1_sm, rng, fast, C.byref(acc))
     state.K = K.value
     return st, acc.value
+
+
+def sm_last_terms() -> dict:
+    """The addends of the last completed split-merge move's log acceptance ratio (kind 0: none),
+    with the keys of Engine.sm_last_terms()."""
+    t = SmTerms()
+    lib().orc_ffi_sm_last_terms(C.byref(t))
+    return {"kind": t.kind, "accepted": t.accepted, "i1": t.i1, "i2": t.i2, "nS": t.nS,
+            "size": list(t.size), "term": list(t.term), "log_prior": t.log_prior,
+            "log_likelihood": t.log_likelihood, "log_proposal": t.log_proposal,
+            "log_ratio": t.log_ratio, "log_u": t.log_u}
 
 
 def run_markov_chain(codes, attrisize, gamma, v, w, *, m=5, iterations=1000, L=1, c_i=None,
