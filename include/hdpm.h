@@ -83,7 +83,7 @@ typedef struct {
      * by the per-start-drift walks (a pick depended on the uniform) */
     int64_t phi_tree_calls, phi_tree_retries;
     /* device pool generations whose entry starts fell back to the sequential host walk (the
-     * segment parse's chain left a window: an entry longer than mean + 14 sd; or debug bit 28) */
+     * segment parse's chain left a window: an entry longer than mean + 14 sd; or HDPM_DBG_POOL_SERIAL_PARSE) */
     int64_t pool_walk_fallbacks;
     /* update_phi speculated on the device beside the sweep (phi_mode device): launched, and
      * committed as the iteration's update (the sweep moved no point) */
@@ -269,44 +269,105 @@ typedef struct {
     double  log_u;           /* log(unif) of sm:591 */
 } hdpm_sm_terms;
 int hdpm_sm_last_terms(const hdpm_ctx* ctx, hdpm_sm_terms* out);
-/* Testing / diagnostics.  mode bit 0: evaluate every point on the exact path (no
- * certainty shortcut); bit 1: print per-phase timings to stderr; bit 2: compute the
- * log-likelihood with the per-point kernel (no regrouping into match counts); bit 3: no
- * snapshot speculation (the resolver decides every uncertain point itself); bit 4: recount
- * the frequency tables every update_phi (no incremental move log); bit 5: accumulate a host
- * timeline of hdpm_iteration (printed to stderr when the context is destroyed); bit 6:
- * generate latent pools with the sequential host generator instead of the device one; bit 7:
- * no speculative update_phi during the sweep; bit 8: no next sweep prepared at the end of
- * an iteration; bit 9: HIP events around every kernel of every launch (per-kernel times);
- * bit 10: the prepass gathers full bound records for latent picks (no pool-entry heads);
- * bit 11: exact rows one wave per point (no workgroup-per-point LDS staging); bit 12: no
- * block mode in the resolver (uncertain points decided one by one); bit 13: block mode for
- * every resolver launch (not only after a launch that listed kResolveBlkMin points); bit 14:
- * wide layouts take the generic prepass (one thread per point) instead of k_prepass_wide; bit 15:
- * the prepared next sweep is launched before the speculative update_phi is started; bit 16:
- * restricted scans of >= 4096 points draw their uniforms on the host (not from the device
- * generator windows); bit 17: a sweep prepared at the end of hdpm_iterations does not start
- * its prepass on the device; bit 18: the prepass certifies "stay" by the margin only (not by
- * the draw's uniform, kernels.hip stay_by_uniform); bit 19: update_phi on the host (the job
- * speculated during the sweep) even when the device update is selected (HDPM_OPT_PHI_DEVICE
- * or HDPM_PHI=device; csrc/phi.hip); bit 20: no lookahead copy of the next update's stream
- * slice (it is copied when the next sweep's draws are reserved); bit 21: the iteration
- * commits the new tables and computes the log-likelihood before it prepares the next sweep
- * (by default the next speculative update_phi is started first); bit 22: no next sweep
- * enqueued while the iteration's update is drawn (gated on the device, k_pipe_wait); bit 23:
- * the one-wave resolvers (LIST mode, block mode after many exact decisions) instead of the
- * fixed-point resolver k_resolve_fp (which bits 0, 12 and 13 also turn off); bit 24: with the
- * fixed-point resolver too, a launch after one that decided many points itself lists every
- * point (no certification by the draw's uniform), as the one-wave resolvers always do; bit 25:
- * the fixed-point resolver for every launch it fits (by default a launch after one that listed
- * fewer than 64 points -- a converged chain -- takes the one-wave LIST resolver); bit 26: the
- * fixed-point resolver's first round starts every point from "stay" instead of its snapshot
- * draw's outcome; bit 27: the device update_phi resolves its drifts by the per-start-drift walks
- * (k_phi_cwalk) instead of the composition trees (k_phi_tree); bit 28: the device pool generator's
- * entry starts by the sequential host walk instead of the segment parse (k_pool_seg*);
- * bit 29: the fixed-point resolver on one workgroup (k_resolve_fp) even after a launch that
- * listed many points (by default those take the device-wide k_resolve_fpg); bit 30: k_resolve_fpg
- * for every fixed-point launch (testing: also the launches with few listed points). */
+/* Testing / diagnostics: the bits of hdpm_set_debug's mode.  Same chain with any of them; each
+ * selects which path computes it.  Every effect the engine gives a bit is listed with it (a bit
+ * that also gates a neighbouring path keeps its number: profiles and A/B records name the values).
+ * Changing the mode drops a prepared next sweep. */
+/* every point on the exact path (no certainty shortcut: every point listed, no certification by
+ * the draw's uniform, no dense listing); the resolver decides each by the exact draw, one by
+ * one: no block mode, no fixed-point resolver */
+#define HDPM_DBG_EXACT_ALL               (1u << 0)
+/* per-phase timings on stderr: host marks of hdpm_iteration, HIP events around every kernel of
+ * every launch, the resolvers' own phase clocks, and the general device update_phi's drift
+ * tables (read back with blocking copies) */
+#define HDPM_DBG_PHASE_TIMES             (1u << 1)
+/* the log-likelihood by the per-point kernel (no regrouping into match counts, not the device
+ * update_phi's sum); the iteration then commits its tables before it prepares the next sweep */
+#define HDPM_DBG_LL_PER_POINT            (1u << 2)
+/* no snapshot speculation (the resolver decides every uncertain point itself); no dense listing */
+#define HDPM_DBG_NO_SNAPSHOT             (1u << 3)
+/* the frequency tables recounted for every update_phi (no incremental move log); hence no
+ * update_phi speculated beside the sweep, on the host or the device, and no next sweep prepared */
+#define HDPM_DBG_RECOUNT                 (1u << 4)
+/* a host timeline of hdpm_iteration accumulated (printed to stderr when the context is
+ * destroyed): host marks, the update job's waits and draw counts, and HIP events around every
+ * kernel of every launch */
+#define HDPM_DBG_TIMELINE                (1u << 5)
+/* latent pools by the sequential host generator instead of the device one; also every device
+ * update_phi off (the chain's, the one speculated beside the sweep, split-merge's) */
+#define HDPM_DBG_HOST_POOL               (1u << 6)
+/* no update_phi speculated during the sweep, on the host or beside it on the device, and a
+ * speculation already made is not used; hence no next sweep prepared, no early go of a sweep
+ * enqueued ahead; split-merge's host update of a wide pair (d >= 128) stays on the one-pass
+ * path (cluster by cluster, no host job) */
+#define HDPM_DBG_NO_SPEC_PHI             (1u << 7)
+/* no next sweep prepared at the end of an iteration */
+#define HDPM_DBG_NO_PREPARE              (1u << 8)
+/* HIP events around every kernel of every launch (per-kernel times; by default the prepass of
+ * every 8th launch only) */
+#define HDPM_DBG_KERNEL_EVENTS           (1u << 9)
+/* the prepass gathers full bound records for latent picks (no pool-entry heads); hence no latent
+ * kept as a head bound by the exact rows */
+#define HDPM_DBG_NO_POOL_HEADS           (1u << 10)
+/* exact rows one wave per point (no workgroup-per-point LDS staging, no mass kernels); no dense
+ * listing */
+#define HDPM_DBG_EXACT_WAVE              (1u << 11)
+/* no block mode in the resolver (uncertain points decided one by one) and no fixed-point
+ * resolver; the host update job takes all of a cluster's logits before its first draw */
+#define HDPM_DBG_NO_BLOCK_MODE           (1u << 12)
+/* block mode for every resolver launch (not only after a launch that listed kResolveBlkMin
+ * points); no fixed-point resolver */
+#define HDPM_DBG_BLOCK_MODE_ALWAYS       (1u << 13)
+/* wide layouts take the generic prepass (one thread per point) instead of k_prepass_wide */
+#define HDPM_DBG_NO_WIDE_PREPASS         (1u << 14)
+/* the prepared next sweep is launched before the speculative host update_phi is started */
+#define HDPM_DBG_SWEEP_FIRST             (1u << 15)
+/* restricted scans of >= 4096 points draw their uniforms on the host (not from the device
+ * generator windows); also split-merge's device update_phi off */
+#define HDPM_DBG_SM_HOST_DRAWS           (1u << 16)
+/* a sweep prepared at the end of hdpm_iterations does not start its prepass on the device */
+#define HDPM_DBG_NO_PREPASS_AHEAD        (1u << 17)
+/* the prepass certifies "stay" by the margin only (not by the draw's uniform, kernels.hip
+ * stay_by_uniform) */
+#define HDPM_DBG_MARGIN_ONLY             (1u << 18)
+/* update_phi on the host (the job speculated during the sweep) even when the device update is
+ * selected (HDPM_OPT_PHI_DEVICE or HDPM_PHI=device; csrc/phi.hip), split-merge's included */
+#define HDPM_DBG_PHI_HOST                (1u << 19)
+/* no lookahead copy of the next update's stream slice (it is copied when the next sweep's draws
+ * are reserved) */
+#define HDPM_DBG_NO_LOOKAHEAD            (1u << 20)
+/* the iteration commits the new tables and computes the log-likelihood before it prepares the
+ * next sweep (by default the next speculative update_phi is started first); hence no next sweep
+ * enqueued while the update is drawn */
+#define HDPM_DBG_COMMIT_FIRST            (1u << 21)
+/* no next sweep enqueued while the iteration's update is drawn (gated on the device,
+ * k_pipe_wait) */
+#define HDPM_DBG_NO_PIPE                 (1u << 22)
+/* the one-wave resolvers (LIST mode, block mode after many exact decisions) instead of the
+ * fixed-point resolver k_resolve_fp (which EXACT_ALL, NO_BLOCK_MODE and BLOCK_MODE_ALWAYS also
+ * turn off) */
+#define HDPM_DBG_ONE_WAVE_RESOLVER       (1u << 23)
+/* with the fixed-point resolver too, a launch after one that decided many points itself lists
+ * every point (no certification by the draw's uniform), as the one-wave resolvers always do */
+#define HDPM_DBG_FP_LIST_ALL_AFTER_EXACT (1u << 24)
+/* the fixed-point resolver for every launch it fits (by default a launch after one that listed
+ * fewer than 64 points -- a converged chain -- takes the one-wave LIST resolver) */
+#define HDPM_DBG_FP_ALWAYS               (1u << 25)
+/* the fixed-point resolver's first round starts every point from "stay" instead of its snapshot
+ * draw's outcome */
+#define HDPM_DBG_FP_FROM_STAY            (1u << 26)
+/* the device update_phi resolves its drifts by the per-start-drift walks (k_phi_cwalk) instead
+ * of the composition trees (k_phi_tree); its fast path (launch_phi2) is not taken either */
+#define HDPM_DBG_PHI_WALKS               (1u << 27)
+/* the device pool generator's entry starts by the sequential host walk instead of the segment
+ * parse (k_pool_seg*) */
+#define HDPM_DBG_POOL_SERIAL_PARSE       (1u << 28)
+/* the fixed-point resolver on one workgroup (k_resolve_fp) even after a launch that listed many
+ * points (by default those take the device-wide k_resolve_fpg) */
+#define HDPM_DBG_FP_ONE_WG               (1u << 29)
+/* k_resolve_fpg for every fixed-point launch (testing: also the launches with few listed
+ * points) */
+#define HDPM_DBG_FPG_ALWAYS              (1u << 30)
 int hdpm_set_debug(hdpm_ctx* ctx, int32_t mode);
 /* The prepass's pool-entry heads, P entries of wb*Ws + 2 words padded to a power of two
  * (Ws <= 4) or to a multiple of 8 words (wide layouts) (csrc/kernels.hpp "Pool-entry heads",

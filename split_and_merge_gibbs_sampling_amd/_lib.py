@@ -7,6 +7,7 @@ and creating an engine fails loudly if no gfx950 device is visible.
 from __future__ import annotations
 
 import ctypes as C
+import enum
 import os
 import subprocess
 
@@ -44,6 +45,42 @@ OPT_SM_WIDE_WAIT_US = 8
 OPT_SM_CHAIN = 9
 OPT_CAPTURE_DELAY_US = 10
 OPT_PHI_SD_SCALE = 11
+
+
+class Debug(enum.IntFlag):
+    """The bits of hdpm_set_debug's mode (include/hdpm.h HDPM_DBG_*, which describes each)."""
+    EXACT_ALL = 1 << 0
+    PHASE_TIMES = 1 << 1
+    LL_PER_POINT = 1 << 2
+    NO_SNAPSHOT = 1 << 3
+    RECOUNT = 1 << 4
+    TIMELINE = 1 << 5
+    HOST_POOL = 1 << 6
+    NO_SPEC_PHI = 1 << 7
+    NO_PREPARE = 1 << 8
+    KERNEL_EVENTS = 1 << 9
+    NO_POOL_HEADS = 1 << 10
+    EXACT_WAVE = 1 << 11
+    NO_BLOCK_MODE = 1 << 12
+    BLOCK_MODE_ALWAYS = 1 << 13
+    NO_WIDE_PREPASS = 1 << 14
+    SWEEP_FIRST = 1 << 15
+    SM_HOST_DRAWS = 1 << 16
+    NO_PREPASS_AHEAD = 1 << 17
+    MARGIN_ONLY = 1 << 18
+    PHI_HOST = 1 << 19
+    NO_LOOKAHEAD = 1 << 20
+    COMMIT_FIRST = 1 << 21
+    NO_PIPE = 1 << 22
+    ONE_WAVE_RESOLVER = 1 << 23
+    FP_LIST_ALL_AFTER_EXACT = 1 << 24
+    FP_ALWAYS = 1 << 25
+    FP_FROM_STAY = 1 << 26
+    PHI_WALKS = 1 << 27
+    POOL_SERIAL_PARSE = 1 << 28
+    FP_ONE_WG = 1 << 29
+    FPG_ALWAYS = 1 << 30
+
 
 STATUS = {0: "OK", 1: "E_VALIDATE", 2: "E_GSL", 3: "E_PROB", 4: "E_WALKER", 5: "E_ARG",
           6: "E_DEVICE", 7: "E_NODEVICE"}

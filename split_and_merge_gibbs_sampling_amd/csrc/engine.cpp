@@ -177,7 +177,7 @@ static void segv_trace(int sig, siginfo_t* info, void* uctx) {
   raise(sig);
 }
 static const bool g_segv_trace = [] {
-  if (!std::getenv("HDPM_SEGV_TRACE")) return false;
+  if (!sw::get<sw::SEGV_TRACE>()) return false;
   Dl_info di;
   if (dladdr((void*)&segv_put_hex, &di)) g_lib_base = (uintptr_t)di.dli_fbase;
   void* warm[2];
@@ -394,9 +394,7 @@ class HostPool {
 
  private:
   explicit HostPool(const std::vector<int>& home) : home_(home) {
-    if (const char* e = std::getenv("HDPM_SPIN_US")) spin_us_ = std::max(0, std::atoi(e));
-    int T = 0;
-    if (const char* e = std::getenv("HDPM_HOST_THREADS")) T = std::atoi(e);
+    int T = sw::get<sw::HOST_THREADS>();
     if (T <= 0) {
       unsigned h = std::thread::hardware_concurrency();
       T = (int)std::min<unsigned>(h ? h : 4, 8);
@@ -412,8 +410,7 @@ class HostPool {
   // cores every iteration): the pool's home domain (the GPU's, hdpm_ctx_create), else the
   // creating thread's; HDPM_PIN_THREADS=0 leaves placement to the OS.
   void pin_workers() {
-    if (const char* e = std::getenv("HDPM_PIN_THREADS"))
-      if (std::atoi(e) == 0) return;
+    if (!sw::get<sw::PIN_THREADS>()) return;
     cpu_set_t allowed;
     if (sched_getaffinity(0, sizeof(allowed), &allowed) != 0) return;
     const std::string base = "/sys/devices/system/cpu/cpu";
@@ -539,7 +536,8 @@ class HostPool {
   std::function<void(int)> bjob_;
   std::function<void(int)>* bcast_ = nullptr;
   std::atomic<bool> stop_{false};
-  int spin_us_ = 2000;   // an iteration's host phases are ~1 ms apart: stay awake between them
+  // (HDPM_SPIN_US, default 2000) an iteration's host phases are ~1 ms apart: stay awake between them
+  const int spin_us_ = sw::get<sw::SPIN_US>();
   int main_cpu_ = -1;    // the calling thread's core (kept free of workers)
   std::vector<int> home_;   // CPUs of the L3 domain the pool lives on (empty: the creator's)
 
@@ -564,8 +562,7 @@ struct PoolScope {
 // started on.  Empty (creating thread's domain) when the topology is not readable.
 static std::vector<int> gpu_home_domain(int device) {
   std::vector<int> none;
-  if (const char* e = std::getenv("HDPM_PIN_THREADS"))
-    if (std::atoi(e) == 0) return none;
+  if (!sw::get<sw::PIN_THREADS>()) return none;
   int cnt = 0;
   if (hipGetDeviceCount(&cnt) != hipSuccess || device < 0 || device >= cnt) return none;
   auto local_list = [](int dev) {
@@ -894,7 +891,7 @@ struct Ctx {
   DevBuf<int4> d_rq;
   DevBuf<uint64_t> d_csum;            // per-label cluster summary for the prepass
   DevBuf<unsigned> d_hist_part;
-  DevBuf<long long> d_rprof;          // resolver phase times (debug mode bit 1)
+  DevBuf<long long> d_rprof;          // resolver phase times (HDPM_DBG_PHASE_TIMES)
   DevBuf<int> d_fpg;                   // k_resolve_fpg's cross-workgroup scratch
   DevBuf<int> d_wide_ctr;              // k_prepass_wide's chunk counter, k_exact_rows_mass's point counter
   DevBuf<int> d_warm;                  // zero gate word and scratch of warm_launch_kernels
@@ -926,13 +923,6 @@ struct Ctx {
   int next_seq() {
     round_seq = round_seq == INT_MAX ? 1 : round_seq + 1;
     return round_seq;
-  }
-  static bool res_word_on() {
-    static const bool on = [] {
-      const char* e = std::getenv("HDPM_RES_WORD");
-      return !(e && e[0] == '0');
-    }();
-    return on;
   }
   // The host's wait for the round of control block q.  By the word: a spin on ResolveCtl::seq
   // (the block and the summary behind it are final when it holds the round's number); past the
@@ -1027,10 +1017,7 @@ struct Ctx {
   // chain's one-cluster device updates cost ~100 us each at C4 against ~45 us per cluster on the
   // host job, profiles/r06/sm_chain/ -- 1 on; >= 2 testing: the chain stops at step
   // sm_chain_mode - 2, split_merge.inl sm_chain; HDPM_SM_CHAIN=1 in the environment turns it on)
-  int sm_chain_mode = [] {
-    const char* e = std::getenv("HDPM_SM_CHAIN");
-    return (e && e[0] == '1') ? 1 : 0;
-  }();
+  int sm_chain_mode = sw::get<sw::SM_CHAIN>();
   bool deep_ok = false;                // set by iteration(): the next sweep may be enqueued ahead
   static constexpr size_t kCtlInts = 16;
   static_assert(sizeof(ResolveCtl) <= kCtlInts * sizeof(int), "control block");
@@ -1058,11 +1045,11 @@ struct Ctx {
   // takes masked (subset) histograms.
   DevBuf<unsigned> d_freq, d_freq2, d_freq_m;
   bool freq_dev_valid = false;
-  // Debug bit 4 (value 16) recounts the tables for every update_phi instead of carrying them
+  // HDPM_DBG_RECOUNT recounts the tables for every update_phi instead of carrying them
   // through the sweep by the move log (the move log then does not run).  The carried tables
   // are used at every N: a sweep whose last point opened a cluster used to skip the sweep-end
   // kernels (kernels.hip sweep_done), which left the tables, and the labels, un-updated.
-  bool recount_only() const { return (debug & 16) != 0; }
+  bool recount_only() const { return (debug & HDPM_DBG_RECOUNT) != 0; }
   uint64_t freq_d2h_version = 0;      // labels_version whose freq copy the sweep already started
   DevBuf<int> d_mlog, d_mcount;
   PinBuf<unsigned> h_freq;
@@ -1081,13 +1068,13 @@ struct Ctx {
   // prepass timing of a sweep enqueued ahead (per control block: read one iteration later)
   bool pre_timed[2] = {false, false};
   hipEvent_t ev_pp[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
-  int debug = 0;
-  // debug bit 1: per-iteration host timeline
+  int debug = 0;                      // hdpm_set_debug: HDPM_DBG_* bits
+  // host marks of one iteration: PHASE_TIMES prints them, TIMELINE sums them
   std::vector<std::pair<const char*, std::chrono::steady_clock::time_point>> trace;
   void mark(const char* what) {
-    if (debug & 34) trace.emplace_back(what, std::chrono::steady_clock::now());
+    if (debug & (HDPM_DBG_PHASE_TIMES | HDPM_DBG_TIMELINE)) trace.emplace_back(what, std::chrono::steady_clock::now());
   }
-  // debug bit 5: accumulate the per-iteration timeline (no extra synchronisation); printed
+  // HDPM_DBG_TIMELINE: accumulate the per-iteration timeline (no extra synchronisation); printed
   // by the context's destructor
   std::vector<std::pair<std::string, double>> trace_sum;
   std::vector<std::vector<float>> trace_smp;   // per trace_sum entry: the samples (median / p90)
@@ -1102,7 +1089,7 @@ struct Ctx {
     trace_smp[q].push_back((float)us);
   }
   int64_t trace_iters = 0, trace_alloc0 = -1, trace_slow = 0;
-  char spec_line[192] = {0};          // the last joined speculative update's stamps (debug bit 5)
+  char spec_line[192] = {0};          // the last joined speculative update's stamps (HDPM_DBG_TIMELINE)
   std::unordered_map<uint64_t, bool> beta_cache;
 
   SmWork sm;
@@ -1304,11 +1291,7 @@ struct Ctx {
   // Jump polynomials z^(624 * bpg * g) mod phi for g < G, built once per window size class
   // and checked on the host against direct twisting.
   void ensure_jump(int64_t count) {
-    static const int G = [] {
-      const char* e = std::getenv("HDPM_MT_WORKGROUPS");
-      const int g = e ? std::atoi(e) : 0;
-      return g >= 2 && g <= 4096 ? g : 256;
-    }();
+    const int G = sw::get<sw::MT_WORKGROUPS>();
     if (count < (int64_t)G * 624 * 8) return;
     if (mt_G == G && count <= (int64_t)624 * G * mt_bpg) return;
     // headroom so later, slightly larger windows (sweep + draws between sweeps) reuse it
@@ -1512,7 +1495,7 @@ struct Ctx {
   // after at most a slice's worth of this update's), copied now: off the iteration's
   // critical path, and landed by the time the next sweep's draws are reserved.
   void phi_lookahead() {
-    if (!look_from || (debug & 1048576)) return;
+    if (!look_from || (debug & HDPM_DBG_NO_LOOKAHEAD)) return;
     const uint64_t from = look_from;
     look_from = 0;
     for (auto& sl : phis)
@@ -1999,13 +1982,13 @@ struct Ctx {
   // la:74-77 / la:124-128: per entry D centers then D sigmas, from the context stream.
   // The device generator (pool_gen.hpp) when the attributes qualify and the host libm is
   // the one glibc_math.hpp reproduces; the sequential host generator otherwise (or with
-  // debug bit 6).  Both leave the same pool and the same stream position.
+  // HDPM_DBG_HOST_POOL).  Both leave the same pool and the same stream position.
   int generate_pool(int64_t P_) {
     if (!n) { err = "set_data first"; return kArg; }
     if (P_ <= 0 || P_ > 0x7fffffff) { err = "pool size must be in 1..2^31-1"; return kArg; }
     auto t0 = std::chrono::steady_clock::now();
     int st = -1;
-    if (!(debug & 64) && glibc_selfcheck()) st = generate_pool_device(P_);
+    if (!(debug & HDPM_DBG_HOST_POOL) && glibc_selfcheck()) st = generate_pool_device(P_);
     if (st < 0) st = generate_pool_host(P_);
     stats.pool_calls++;
     stats.pool_entries += P_;
@@ -2146,8 +2129,8 @@ struct Ctx {
       int64_t end = pg.h_starts.p[P_];
       const int werr = *pg.h_err.p;
       if (werr & 8) end = -1;
-      if (!(werr & 8) && (werr & 4 || (debug & 268435456))) {
-        // the chain left a window (or debug bit 28): the sequential walk
+      if (!(werr & 8) && (werr & 4 || (debug & HDPM_DBG_POOL_SERIAL_PARSE))) {
+        // the chain left a window (or HDPM_DBG_POOL_SERIAL_PARSE): the sequential walk
         pg.walk_fallbacks++;
         stats.pool_walk_fallbacks++;
         pg.h_bm.ensure((size_t)nc * 2 * nwords);
@@ -2293,67 +2276,21 @@ struct Ctx {
   // after a prefix launched with the same arguments and no state change in between).
   enum { kRoundAll = 0, kRoundPrefix = 1, kRoundResolve = 2 };
   static constexpr int kFpMinListed = 64;
-  static constexpr int kFpgMinListed = 1024;   // listed points of the previous launch for k_resolve_fpg (two chunks)
   static constexpr int kMassNoSpec = 65536;    // expected listed points above which no snapshot draws are made
-  // HDPM_FPG_MIN: the listed points (expected) from which launches take k_resolve_fpg (A/B)
-  static int fpg_min_listed() {
-    static const int v = [] {
-      const char* e = std::getenv("HDPM_FPG_MIN");
-      return e ? std::max(1, std::atoi(e)) : (int)kFpgMinListed;
-    }();
-    return v;
-  }
   static constexpr int kDenseMinPoints = 4096;  // dense listing only for launches over at least this many points
   // the state fits the dense path: the fixed-point resolvers and a mass exact-rows kernel
   // (kernels.hip launch_exact_rows: the thread-per-point kernel's LDS tables, or the
   // wave-per-point kernel's)
   bool dense_list_fits(int m, int nslots) const {
     const int lcap = std::min(scap, nslots + 2);
-    if (!fp_eligible(K + m, lcap) || (debug & (2048 | 8))) return false;
+    if (!fp_eligible(K + m, lcap) || (debug & (HDPM_DBG_EXACT_WAVE | HDPM_DBG_NO_SNAPSHOT))) return false;
     const size_t lanes_lds = (size_t)K * (2 * (size_t)d * 8 + (size_t)nq * 16);
     const size_t mass_lds = (size_t)K * 2 * d * 8 + (size_t)8 * m * d * 8 + (size_t)K * nq * 16 + (size_t)8 * nq * 16;
     return (nq <= 8 && K <= 64 && lanes_lds <= 64 * 1024) || mass_lds <= 96 * 1024;
   }
-  static bool fp_unsettled_unif() {
-    static const bool on = [] {
-      const char* e = std::getenv("HDPM_FP_UNSETTLED_UNIF");
-      return !(e && std::atoi(e) == 0);
-    }();
-    return on;
-  }
-  // HDPM_DENSE_DIRECT=0: dense launches still run the prepass (A/B)
-  static bool dense_direct_on() {
-    static const bool on = [] {
-      const char* e = std::getenv("HDPM_DENSE_DIRECT");
-      return !(e && std::atoi(e) == 0);
-    }();
-    return on;
-  }
-  // HDPM_LAT_BOUND=0: every latent column exact in the level-table rows (A/B)
-  static bool lat_bound_on() {
-    static const bool on = [] {
-      const char* e = std::getenv("HDPM_LAT_BOUND");
-      return !(e && std::atoi(e) == 0);
-    }();
-    return on;
-  }
-  static bool lv_spec_on() {
-    static const bool on = [] {
-      const char* e = std::getenv("HDPM_LV_SPEC");
-      return !(e && std::atoi(e) == 0);
-    }();
-    return on;
-  }
-  // HDPM_DENSE_LIST=0: no dense listing (A/B)
-  static bool dense_list_on() {
-    static const bool on = [] {
-      const char* e = std::getenv("HDPM_DENSE_LIST");
-      return !(e && std::atoi(e) == 0);
-    }();
-    return on;
-  }
-  bool fp_eligible(int E, int lcap) const {
-    return E <= 64 && lcap <= 64 && !(debug & (1 | 4096 | 8192 | 8388608));
+  bool fp_eligible(int E, int lcap) const {   // (off under the bits that ask for a one-wave mode)
+    return E <= 64 && lcap <= 64 && !(debug & (HDPM_DBG_EXACT_ALL | HDPM_DBG_NO_BLOCK_MODE |
+                                               HDPM_DBG_BLOCK_MODE_ALWAYS | HDPM_DBG_ONE_WAVE_RESOLVER));
   }
   // pg: a sweep enqueued ahead (pre_enqueue) -- its kernels take the gate and the draws
   // from pg, its control block is cpar; no timing events, no counters.
@@ -2377,7 +2314,7 @@ struct Ctx {
     // drift -- a re-test failure restarted the launch, and its prepass and exact rows, at that
     // point (C5 from a random start: ~118 certified points per sweep restarted ~700k rows)
     const bool dense_list = dense_fits && el >= kDenseMinPoints && 2 * (int64_t)el >= (int64_t)(n - p) &&
-                            !(debug & 1) && dense_list_on();
+                            !(debug & HDPM_DBG_EXACT_ALL) && sw::get<sw::DENSE_LIST>();
     // the resolver writes its control block and summary straight into host memory
     if (h_ctl.n < 2 * ctl_stride()) {
       h_ctl.ensure(2 * ctl_stride(), hipHostMallocCoherent);
@@ -2388,7 +2325,7 @@ struct Ctx {
     // HIP events between kernels cost a dispatch gap each: the prepass is timed on every
     // 8th launch (all launches, and the other kernels too, in the diagnostic modes)
     if (part != kRoundResolve && !pg) {
-      round_fine = (debug & (2 | 32 | 512)) != 0;
+      round_fine = (debug & (HDPM_DBG_PHASE_TIMES | HDPM_DBG_TIMELINE | HDPM_DBG_KERNEL_EVENTS)) != 0;
       round_timed = round_fine || (launch_count++ % 8 == 0);
     }
     const int S = nslots;
@@ -2411,30 +2348,31 @@ struct Ctx {
     pa.pool = ParamTables{d_pool_codes.p, d_pool_tab.p};
     pa.P = P; pa.raw = d_sweep_raw; pa.m = m; pa.logn = d_logn.p; pa.logfac = std::log(gamma / m);
     pa.xbs = d_xbs.p; pa.Ws = Ws; pa.wb = wb; pa.slot_bnd = d_slot_bnd.p; pa.pool_bnd = d_pool_bnd.p; pa.bw = bw;
-    pa.pool_head = (head_fits(wb, Ws) && !(debug & 1024)) ? d_pool_head.p : nullptr;
+    pa.pool_head = (head_fits(wb, Ws) && !(debug & HDPM_DBG_NO_POOL_HEADS)) ? d_pool_head.p : nullptr;
     pa.head_ha = head_ha;
     pa.head_hb = head_hb;
     d_csum.ensure((size_t)std::max(K, 1) * (bw + 2));
     pa.csum = d_csum.p;
 
-    pa.thresh = ((debug & 1) || dense_list) ? INFINITY : T + 2.0 * dmax;
+    pa.thresh = ((debug & HDPM_DBG_EXACT_ALL) || dense_list) ? INFINITY : T + 2.0 * dmax;
     pa.thresh_ref = T + 2.0 * dmax;
     // certification by the draw's uniform only while the chain is settled: after a launch
     // that exceeded its drift budget, restarted or decided many points itself, uniform-
     // certified points (no exact rows) would fail re-verification and restart the launch
     // (the fixed-point resolver re-tests and restarts cheaply enough to keep the uniform
-    // certification after many exact decisions; debug bit 24 lists every point there too)
+    // certification after many exact decisions; HDPM_DBG_FP_LIST_ALL_AFTER_EXACT lists every point there too)
     const bool fp_next = fp_eligible(K + m, std::min(scap, nslots + 2)) &&
-                         (el < 0 || el >= kFpMinListed || (debug & 33554432));
-    const bool many_exact = last_exact >= kResolveBlkMin && (!fp_next || (debug & 16777216));
+                         (el < 0 || el >= kFpMinListed || (debug & HDPM_DBG_FP_ALWAYS));
+    const bool many_exact = last_exact >= kResolveBlkMin && (!fp_next || (debug & HDPM_DBG_FP_LIST_ALL_AFTER_EXACT));
     // The fixed-point resolvers keep the uniform's certification after an unsettled launch
     // (a restart behind a new cluster, a drift past the budget): a point it certified that no
     // longer holds is re-tested and restarts the launch, which these resolvers do cheaply,
     // while listing every uncertain point by margin alone cost C2's restart launches ~5x the
     // points (3,106 vs ~530) and ~300 us each (HDPM_FP_UNSETTLED_UNIF=0: margins only, as the
     // one-wave resolvers need)
-    const bool unsettled_margins = last_unsettled && !(fp_next && fp_unsettled_unif());
-    pa.dmax2_ref = ((debug & (1 | 262144)) || unsettled_margins || many_exact) ? INFINITY : 2.0 * dmax;
+    const bool unsettled_margins = last_unsettled && !(fp_next && sw::get<sw::FP_UNSETTLED_UNIF>());
+    const bool margins_only = (debug & (HDPM_DBG_EXACT_ALL | HDPM_DBG_MARGIN_ONLY)) || unsettled_margins || many_exact;
+    pa.dmax2_ref = margins_only ? INFINITY : 2.0 * dmax;
     pa.dmax2 = dense_list ? INFINITY : pa.dmax2_ref;
     if (dense_list && !pg && part != kRoundResolve) stats.dense_launches++;
     pa.L = d_L.p; pa.rowpos = d_rowpos.p; pa.margin = d_margin.p; pa.list = d_list.p; pa.cnt = d_cnt.p;
@@ -2444,25 +2382,25 @@ struct Ctx {
     // its first round anyway, and the mass exact-rows kernel is ~20% faster without them
     // (with the level-table exact rows the snapshot draws are made behind the rows by
     // k_snap_draws, a thread per point, also for dense launches; HDPM_LV_SPEC=0: not there)
-    pa.spec_lv = lv_spec_on() ? 1 : 0;
+    pa.spec_lv = sw::get<sw::LV_SPEC>() ? 1 : 0;
     // latents far below the clusters kept as head bounds by the level-table exact rows; only
     // for the fixed-point resolvers (their draws and the serial path take the bounds,
     // kernels.hip latent_fix), with pool-entry heads
-    pa.lbound = (fp_next && pa.pool_head && m <= 32 && lat_bound_on()) ? 1 : 0;
+    pa.lbound = (fp_next && pa.pool_head && m <= 32 && sw::get<sw::LAT_BOUND>()) ? 1 : 0;
     d_lmask.ensure((size_t)((n + kBlock - 1) / kBlock) * kBlock);
     pa.lmask = d_lmask.p;
     pa.lat_negl = lat_negl;
     pa.exact_pref = exact_pref;
     // a dense launch needs no bounds: its list is every point (k_dense_list)
-    pa.dense_direct = dense_list && dense_direct_on() ? 1 : 0;
-    pa.spec = ((debug & 8) || (el >= kMassNoSpec && !pa.spec_lv)) ? nullptr : d_spec.p;
+    pa.dense_direct = dense_list && sw::get<sw::DENSE_DIRECT>() ? 1 : 0;
+    pa.spec = ((debug & HDPM_DBG_NO_SNAPSHOT) || (el >= kMassNoSpec && !pa.spec_lv)) ? nullptr : d_spec.p;
     pa.spec_rad = d_spec_rad.p;
     pa.rq = d_rq.p;
     pa.p0 = p;
-    pa.exact_wave = (debug & 2048) ? 1 : 0;
+    pa.exact_wave = (debug & HDPM_DBG_EXACT_WAVE) ? 1 : 0;
     pa.exact_grid = el < 0 ? 0 : std::min(1536, std::max(64, el + 64));
     pa.exact_scan = el >= 4096 ? 1 : 0;
-    pa.wide = (debug & 16384) ? 0 : 1;
+    pa.wide = (debug & HDPM_DBG_NO_WIDE_PREPASS) ? 0 : 1;
     pa.zero = nullptr;
     d_wide_ctr.ensure(4);
     pa.wide_ctr = d_wide_ctr.p;      // cleared by k_cluster_summary (below: K > 0)
@@ -2518,31 +2456,32 @@ struct Ctx {
     ra.rq = pa.rq;
     ra.nblocks = nblocks; ra.p0 = p; ra.T = T; ra.dmax = dmax; ra.scap = scap; ra.K = K;
     ra.lcap = std::min(scap, nslots + 2);
-    ra.nslots = nslots; ra.ctl = ctl_at(cpar); ra.summary = (int*)ctl_at(cpar) + kCtlInts; ra.force_exact = (debug & 1);
+    ra.nslots = nslots; ra.ctl = ctl_at(cpar); ra.summary = (int*)ctl_at(cpar) + kCtlInts;
+    ra.force_exact = (debug & HDPM_DBG_EXACT_ALL) ? 1 : 0;
     ra.prof = nullptr;
     ra.mlog = track ? d_mlog.p : nullptr;
     ra.mcount = track ? d_mcount.p : nullptr;
     ra.freq = track ? d_freq.p : nullptr;
     ra.fstride = d * mmax;
-    if ((debug & 2) && !pg) {
+    if ((debug & HDPM_DBG_PHASE_TIMES) && !pg) {
       d_rprof.ensure(16);
       ra.prof = d_rprof.p;
     }
     // block mode when in the previous launch many uncertain points had to be decided one by
     // one (their snapshot draws no longer held: an unconverged chain, or clusters appearing
     // and vanishing); LIST mode passes over the rest in one ballot per 64
-    ra.blocks = (K + m <= 64 && nslots <= 64 && !(debug & 4096) && !(debug & 1) &&
-                 ((debug & 8192) || last_exact >= kResolveBlkMin)) ? 1 : 0;
-    // the fixed-point resolver whenever the state fits it (debug bit 23: the one-wave LIST /
+    ra.blocks = (K + m <= 64 && nslots <= 64 && !(debug & HDPM_DBG_NO_BLOCK_MODE) && !(debug & HDPM_DBG_EXACT_ALL) &&
+                 ((debug & HDPM_DBG_BLOCK_MODE_ALWAYS) || last_exact >= kResolveBlkMin)) ? 1 : 0;
+    // the fixed-point resolver whenever the state fits it (HDPM_DBG_ONE_WAVE_RESOLVER: the one-wave LIST /
     // block modes; bits 12 / 13 select those modes and keep them)
     // (a launch whose predecessor listed only a few points -- a converged chain -- keeps the
     // one-wave LIST resolver: its fixed cost is half the fixed-point kernel's, ~7 vs ~13 us at C5)
-    ra.fp = (fp_eligible(K + m, ra.lcap) && (el < 0 || el >= kFpMinListed || (debug & 33554432)))
+    ra.fp = (fp_eligible(K + m, ra.lcap) && (el < 0 || el >= kFpMinListed || (debug & HDPM_DBG_FP_ALWAYS)))
                 ? 1 : 0;
     if (ra.fp) ra.blocks = 0;
-    ra.debug_fp = (debug & 67108864) ? 1 : 0;
+    ra.debug_fp = (debug & HDPM_DBG_FP_FROM_STAY) ? 1 : 0;
     // the device-wide fixed-point resolver (k_resolve_fpg) after a launch that listed many
-    // points: one 512-point chunk per workgroup, a workgroup per CU (debug bit 29: one workgroup)
+    // points: one 512-point chunk per workgroup, a workgroup per CU (HDPM_DBG_FP_ONE_WG: one workgroup)
     ra.fpg = 0;
     ra.fpg_buf = nullptr;
     // (k_snap_draws, behind the level-table exact rows, counted them)
@@ -2556,8 +2495,8 @@ struct Ctx {
     ra.fpg_fail = fpg_fail_at;
     const bool fpg_skipped = fpg_skip && part != kRoundPrefix;
     if (fpg_skipped) fpg_skip = false;
-    if (ra.fp && !fpg_skipped && (el >= fpg_min_listed() || (debug & 1073741824)) && !(debug & 536870912) &&
-        ra.lcap <= 64) {
+    if (ra.fp && !fpg_skipped && (el >= sw::get<sw::FPG_MIN>() || (debug & HDPM_DBG_FPG_ALWAYS)) &&
+        !(debug & HDPM_DBG_FP_ONE_WG) && ra.lcap <= 64) {
       int& mg = fpg_grid(ra.lcap, m);
       if (mg == 0) {
         mg = resolve_fpg_max_grid(ra.lcap, m);
@@ -2591,7 +2530,7 @@ struct Ctx {
     }
     // the round's end for the host: the sequence word for a round enqueued ahead, else the event
     ra.seq = pg ? pipe_seq : next_seq();
-    const bool by_word = pg && res_word_on();
+    const bool by_word = pg && sw::get<sw::RES_WORD>();
     HIPCHK(launch_resolve(ra, stream));
     mark("r.resolve");
     if (fine) HIPCHK(hipEventRecord(ev[2], stream));
@@ -2645,7 +2584,8 @@ struct Ctx {
   // a launched sweep cannot be cancelled), round 0 of the sweep is launched too, so the
   // device goes on from this iteration's uploads without waiting for the host.
   void prepare_next_sweep(int m, bool launch) {
-    if (ahead.active || !have_state || P <= 0 || m <= 0 || tables_dirty || (debug & (256 | 128 | 16))) return;
+    if (ahead.active || !have_state || P <= 0 || m <= 0 || tables_dirty) return;
+    if (debug & (HDPM_DBG_NO_PREPARE | HDPM_DBG_NO_SPEC_PHI | HDPM_DBG_RECOUNT)) return;
     if (!(freq_dev_valid && freq_version == labels_version)) return;
     rng_sync();
     mark("ahead.sync");
@@ -2660,8 +2600,8 @@ struct Ctx {
     ahead.active = true;
     // the speculative update_phi first: its serial draws, not the device sweep, are the
     // longer path (timeline: launching the sweep first cost ~8% of the iteration rate);
-    // debug bit 15 launches the sweep first
-    const bool sweep_first = (debug & 32768) != 0;
+    // HDPM_DBG_SWEEP_FIRST launches the sweep first
+    const bool sweep_first = (debug & HDPM_DBG_SWEEP_FIRST) != 0;
     if (!sweep_first && host_spec()) {
       spec_launch();
       mark("ahead.spec");
@@ -2681,7 +2621,7 @@ struct Ctx {
       // only (scratch outputs: any other call can still drop the prepared sweep)
       if (launch) {
         if (launch_round(0, K, m, ahead.raw, ahead.track) == kOk) ahead.launched = true;
-      } else if (!(debug & 131072)) {
+      } else if (!(debug & HDPM_DBG_NO_PREPASS_AHEAD)) {
         // hdpm_synchronize waits for the chain's work up to here, not for the prepared prefix
         HIPCHK(hipEventRecord(ev[7], stream));
         if (launch_round(0, K, m, ahead.raw, ahead.track, kRoundPrefix) == kOk) ahead.prefix = true;
@@ -2755,16 +2695,12 @@ struct Ctx {
       }
     }
     // the device's own go (PipeAuto) when the speculated update is the fast path's: the wait
-    // kernel goes behind the update's completion and reads its chain word
-    static const bool auto_env_off = [] {
-      const char* e = std::getenv("HDPM_PIPE_AUTO");
-      return e && e[0] == '0';
-    }();
+    // kernel goes behind the update's completion and reads its chain word (HDPM_PIPE_AUTO=0: never)
     PipeAuto au{};
     // (not behind a recorded sweep whose labels capture_labels will read from the device: the
     // mirror is invalid now and a sweep leaves it so; the host's go comes after that copy)
     const bool labels_from_device = record_now && !host_c_valid;
-    if (dev && pipe_auto && !auto_env_off && dspec.ran && dspec.fast && dspec.chain && whole >= 0 &&
+    if (sw::get<sw::PIPE_AUTO>() && dev && pipe_auto && dspec.ran && dspec.fast && dspec.chain && whole >= 0 &&
         !labels_from_device) {
       const RngWindow& w = win[whole];
       au = PipeAuto{dspec.chain, w.raw.p, (int64_t)w.start_pos, w.count, (int64_t)n * (m + 1), 1};
@@ -2828,17 +2764,13 @@ struct Ctx {
   // device_draws will pick (the earliest that covers them), which the enqueued kernels must
   // have waited for; the chain's rng is not touched.
   void pipe_early_go(int m, bool track, bool freq_before_ok) {
-    static const bool env_off = [] {
-      const char* e = std::getenv("HDPM_PIPE_EARLY");
-      return e && e[0] == '0';
-    }();
-    if (env_off || !pre.active || !pre.round_ok || pre.dev || pre.au || pre.m != m) return;
+    if (!sw::get<sw::PIPE_EARLY>() || !pre.active || !pre.round_ok || pre.dev || pre.au || pre.m != m) return;
     // (the gate-off test mode keeps its time-out; a recorded sweep's label download stays ahead
     // of any sweep that writes d_c, as for PipeAuto in pre_enqueue)
     if (!pipe_host_check || (record_now && !host_c_valid)) return;
     const StreamAhead& sa = phi_stream;
     // (deep_ok: iteration() defers this update's commit and calls pipe_go with this m)
-    if (!(deep_ok && host_spec() && !(debug & 128))) return;
+    if (!(deep_ok && host_spec() && !(debug & HDPM_DBG_NO_SPEC_PHI))) return;
     if (!(spec.ran && spec.joined && K > 0 && spec.K == K && spec.nvalid == K)) return;
     if (!(spec.pos == rng.pos && spec.epoch == rng.epoch && sa.n > 0 && sa.start.pos == spec.pos)) return;
     if (!(spec.stage_buf >= 0 && spec.stage_buf == stage_hold && spec.stage_buf == pre.buf)) return;
@@ -3009,8 +2941,8 @@ struct Ctx {
     if (tables_dirty) upload_clusters();
     // update_phi can be speculated during the sweep when the host holds the pre-sweep
     // frequency tables of every label and the sweep carries them (move log)
-    const bool spec_go = freq_dev_valid && freq_version == labels_version && !(debug & 128) && !recount_only() &&
-                         host_spec();
+    const bool spec_go = freq_dev_valid && freq_version == labels_version && !(debug & HDPM_DBG_NO_SPEC_PHI) &&
+                         !recount_only() && host_spec();
     const bool freq_before_ok = freq_version == labels_version && !recount_only();
     // or on the device beside the sweep (phi_mode 1)
     const bool dspec_go = freq_dev_valid && freq_version == labels_version && !recount_only() && dspec_on();
@@ -3079,7 +3011,7 @@ struct Ctx {
       if (stats.rounds == rounds0) {   // hidden behind the device work
         // (not while sweeps keep moving points: the enqueued sweep would be dropped)
         if (deep_ok && (host_spec() ? (spec.ran && spec.K == K) : (dspec.ran && dspec.K == K)) && track &&
-            last_sweep_moves == 0 && !(debug & 4194304)) {
+            last_sweep_moves == 0 && !(debug & HDPM_DBG_NO_PIPE)) {
           pre_enqueue(m, track);
           mark("pre");
           enqueued = true;
@@ -3161,7 +3093,7 @@ struct Ctx {
       // the sweep enqueued ahead runs only after a complete sweep without moves
       if (pre.active && (c.status || c.next < n || c.moves)) pre_release();
       last_sweep_rounds = (int)(stats.rounds - rounds0);
-      if ((debug & 2) && last_fp && last_fpg) {
+      if ((debug & HDPM_DBG_PHASE_TIMES) && last_fp && last_fpg) {
         long long tp[16];
         HIPCHK(hipMemcpy(tp, d_rprof.p, sizeof(tp), hipMemcpyDeviceToHost));
         std::fprintf(stderr,
@@ -3169,7 +3101,7 @@ struct Ctx {
                      "re-test / commit %.2f us, in grid barriers %.2f us, total %.2f us\n",
                      last_fpg, tp[9], tp[8], tp[5], (tp[1] - tp[0]) / 100.0, tp[3] / 100.0, tp[4] / 100.0, tp[2] / 100.0,
                      (tp[7] - tp[0]) / 100.0);
-      } else if ((debug & 2) && last_fp) {
+      } else if ((debug & HDPM_DBG_PHASE_TIMES) && last_fp) {
         long long tp[16];
         HIPCHK(hipMemcpy(tp, d_rprof.p, sizeof(tp), hipMemcpyDeviceToHost));
         std::fprintf(stderr,
@@ -3178,7 +3110,7 @@ struct Ctx {
                      "evaluations (slowest wave) %.2f us, %lld evaluations, %lld own draws (row loads + draws: %.2f us, summed over waves)\n",
                      (tp[1] - tp[0]) / 100.0, tp[9], tp[8], tp[5], tp[3] / 100.0, tp[4] / 100.0, tp[6], tp[2] / 100.0,
                      (tp[7] - tp[0]) / 100.0, tp[10] / 100.0, tp[11] / 100.0, tp[12] / 100.0, tp[14], tp[15], tp[13] / 100.0);
-      } else if (debug & 2) {
+      } else if (debug & HDPM_DBG_PHASE_TIMES) {
         long long tp[16];
         HIPCHK(hipMemcpy(tp, d_rprof.p, sizeof(tp), hipMemcpyDeviceToHost));
         std::fprintf(stderr,
@@ -3494,11 +3426,11 @@ struct Ctx {
     int stage_buf = 0;                 // staging buffer phase C fills
     const double* sig_in = nullptr;    // current sigmas (phase A), indexed like Sig
     bool stage = true;                 // phase C stages the label tables into L
-    // diagnostics (debug bit 5): ns after launch
+    // diagnostics (HDPM_DBG_TIMELINE): ns after launch
     std::chrono::steady_clock::time_point t_launch;
     std::atomic<int64_t> ns_fill{0}, ns_logits{0}, ns_b0{0}, ns_b1{0}, ns_f0{0}, ns_f1{0}, ns_f2{0};
-    int64_t ns_wait_a = 0, ns_wait_l = 0;   // (debug bit 5) B's waits for phase A / logit chunks
-    int64_t b_draws = 0, b_clusters_extra = 0;   // (debug bit 5) B's draws, clusters with an extra draw
+    int64_t ns_wait_a = 0, ns_wait_l = 0;   // (HDPM_DBG_TIMELINE) B's waits for phase A / logit chunks
+    int64_t b_draws = 0, b_clusters_extra = 0;   // (HDPM_DBG_TIMELINE) B's draws, clusters with an extra draw
     std::atomic<int> b_thread{0};
   } pj;
   int64_t pj_ns() const {
@@ -3775,10 +3707,10 @@ struct Ctx {
     int c = PhiJob::chunk_of(pos);
     if (c >= nl) return INT64_MAX;
     if (!pj.ldone[c].load(std::memory_order_acquire)) {
-      const int64_t w0 = (debug & 32) ? pj_ns() : 0;
+      const int64_t w0 = (debug & HDPM_DBG_TIMELINE) ? pj_ns() : 0;
       while (!pj.ldone[c].load(std::memory_order_acquire))
         if (!pj_logit()) HostPool::spin_pause();
-      if (debug & 32) pj.ns_wait_l += pj_ns() - w0;
+      if (debug & HDPM_DBG_TIMELINE) pj.ns_wait_l += pj_ns() - w0;
     }
     while (c + 1 < nl && pj.ldone[c + 1].load(std::memory_order_acquire)) ++c;
     return c + 1 >= nl ? INT64_MAX : std::min<int64_t>(sa.n, PhiJob::chunk_beg(c + 1));
@@ -3796,7 +3728,7 @@ struct Ctx {
   bool pj_stream_ready() const {
     if (pj.fill.load(std::memory_order_acquire) != 2) return false;
     const int nl = pj.nL.load(std::memory_order_relaxed);
-    if (debug & 4096) return pj.doneL.load(std::memory_order_acquire) >= nl;   // all logits first
+    if (debug & HDPM_DBG_NO_BLOCK_MODE) return pj.doneL.load(std::memory_order_acquire) >= nl;   // all logits first
     return nl == 0 || pj.ldone[0].load(std::memory_order_acquire);
   }
   // B for every cluster, in order, on the thread that claims it once the stream is ready
@@ -3815,15 +3747,15 @@ struct Ctx {
     for (; tb < pj.T; ++tb) {
       const int64_t u0 = sa.used;
       if (pj.stA[tb].load(std::memory_order_acquire) < pj.nach) {
-        const int64_t w0 = (debug & 32) ? pj_ns() : 0;
+        const int64_t w0 = (debug & HDPM_DBG_TIMELINE) ? pj_ns() : 0;
         while (pj.stA[tb].load(std::memory_order_acquire) < pj.nach)
           if (!pj_take_a()) HostPool::spin_pause();
-        if (debug & 32) pj.ns_wait_a += pj_ns() - w0;
+        if (debug & HDPM_DBG_TIMELINE) pj.ns_wait_a += pj_ns() - w0;
       }
       if (pj.offs) pj.offs[tb] = sa.used;
       pj.berr = pj_phaseB(tb);
       if (pj.berr) break;
-      if (debug & 32) pj.b_clusters_extra += (sa.used - u0) != 3 * (int64_t)d;
+      if (debug & HDPM_DBG_TIMELINE) pj.b_clusters_extra += (sa.used - u0) != 3 * (int64_t)d;
       pj.stB[tb].store(1, std::memory_order_release);
     }
     if (pj.offs && !pj.berr) pj.offs[pj.T] = sa.used;
@@ -3910,7 +3842,7 @@ struct Ctx {
       for (int t = 0; t < nv; ++t)
         if (spec.off[t + 1] > sa.n) { nv = t; break; }
     spec.nvalid = nv;
-    if (debug & 32) {
+    if (debug & HDPM_DBG_TIMELINE) {
       tsum("spec.fill_start", pj.ns_f0.load() * 1e-3);
       tsum("spec.state_at", pj.ns_f1.load() * 1e-3);
       tsum("spec.slice_at", pj.ns_f2.load() * 1e-3);
@@ -4005,7 +3937,7 @@ struct Ctx {
   } phd;
   // update_phi placement: the host job speculated during the sweep (default), or the device
   // (phi.hip, after the sweep): HDPM_OPT_PHI_DEVICE, or HDPM_PHI=device in the environment;
-  // debug bit 19 (value 524288) forces the host.
+  // HDPM_DBG_PHI_HOST forces the host, and so does HDPM_DBG_HOST_POOL (kDbgPhiOnHost).
   // phi_mode: 0 the host job, 1 the device (fast path first), 2 the device's general kernels
   // only, 3 automatic (default): the device for the chain's update_phi when it has at least
   // kPhiAutoItems (cluster, attribute) items -- where the host job's serial draws outlast the
@@ -4013,16 +3945,12 @@ struct Ctx {
   // split-merge's one- and two-cluster updates (C5 / C3: host 7.7k / 12.8k vs device 5.2k / 8.3k,
   // profiles/r06/ab_phi_auto/).  HDPM_PHI=host|device|device-general|auto overrides the default.
   static constexpr int64_t kPhiAutoItems = 4096;
-  int phi_mode = [] {
-    const char* e = std::getenv("HDPM_PHI");
-    if (e && std::strcmp(e, "host") == 0) return 0;
-    if (e && std::strcmp(e, "device") == 0) return 1;
-    if (e && std::strcmp(e, "device-general") == 0) return 2;
-    return 3;
-  }();
+  int phi_mode = sw::phi_mode();
   // update_phi of `items` (cluster, attribute) pairs of the chain on the device?
   bool phi_dev_for(int64_t items) const { return phi_mode == 1 || phi_mode == 2 || (phi_mode == 3 && items >= kPhiAutoItems); }
-  bool host_spec() const { return !phi_dev_for((int64_t)K * d) || (debug & 524288); }
+  // the bits under which no update_phi runs on the device (the chain's, split-merge's)
+  static constexpr unsigned kDbgPhiOnHost = HDPM_DBG_PHI_HOST | HDPM_DBG_HOST_POOL;
+  bool host_spec() const { return !phi_dev_for((int64_t)K * d) || (debug & HDPM_DBG_PHI_HOST); }
   double dev_ll = 0.0;                 // compute_loglikelihood from the last full device update
   uint64_t dev_ll_version = 0;         // labels_version it belongs to (0: none)
 
@@ -4128,11 +4056,8 @@ struct Ctx {
     // (measured, one box, profiles/r06/phi2gs/: C4 T = 10, D = 784 -- gs 8 / 16 / 32 / 64: 6,512 /
     // 6,518 / 6,792 / 5,301 it/s; C5 with the device update, T = 20, D = 128 -- 8 / 16 / 32: 7,244 /
     // 7,566 / 7,163; C3, D = 64 -- 11,308 / 11,164 / 10,044).  HDPM_PHI2_GS forces one (testing).
-    static const int gs_force = [] {
-      const char* e = std::getenv("HDPM_PHI2_GS");
-      const int v = e ? std::atoi(e) : 0;
-      return (v == 8 || v == 16 || v == 32 || v == 64) ? v : 0;
-    }();
+    const int gs_env = sw::get<sw::PHI2_GS>();
+    const int gs_force = (gs_env == 8 || gs_env == 16 || gs_env == 32 || gs_env == 64) ? gs_env : 0;
     if (pl.tW >= 64 && pl.tW < 65535) {
       auto fits = [&](int gs) {
         const int G = (d + gs - 1) / gs;
@@ -4205,7 +4130,7 @@ struct Ctx {
   static constexpr double kPhiFastSd = 4.75;
   PhiPlan fast_plan(int T, bool sm, int min_count, bool* fast) {
     const PhiPlan pf = phi_plan(T, sm, kPhiFastSd / kPhiSd);
-    *fast = phi_fast(pf) && min_count >= 16 && !(debug & 134217728);
+    *fast = phi_fast(pf) && min_count >= 16 && !(debug & HDPM_DBG_PHI_WALKS);
     if (*fast && phd.fast_backoff > 0) {
       --phd.fast_backoff;
       *fast = false;
@@ -4214,9 +4139,9 @@ struct Ctx {
   }
   // the general kernels' composition trees, unless a cluster is small enough for a pick to depend
   // on the uniform (with one walk segment per cluster, d <= 128, such clusters are walked inside
-  // the tree-mode update itself); debug bit 27: always the per-start-drift walks
+  // the tree-mode update itself); HDPM_DBG_PHI_WALKS: always the per-start-drift walks
   bool phi_tree_for(const PhiPlan& pl, int min_count) const {
-    return pl.tree_ok && (pl.S == 1 || min_count >= phd.tree_min_count) && !(debug & 134217728);
+    return pl.tree_ok && (pl.S == 1 || min_count >= phd.tree_min_count) && !(debug & HDPM_DBG_PHI_WALKS);
   }
 
   // ---- the outcome of one device update (phi_host.hpp: PhiOutView, phi_rerun_mode) ----
@@ -4355,7 +4280,7 @@ struct Ctx {
       a.gs = pl.gs; a.G = pl.G; a.gtab2 = phd.gtab2.p; a.roots = phd.roots.p; a.ctr = phd.ctr.p; a.gen = phd.gen;
       a.tree = nullptr;
       a.lg = nullptr; a.lzz = nullptr;                   // the fast path computes its logits itself
-      if (std::getenv("HDPM_PHI_TIMING")) {
+      if (sw::get<sw::PHI_TIMING>()) {
         // testing: phase marks of the fast path (printed after a synchronous device update)
         if (!phd.tdbg.p) phd.tdbg.ensure(24);
         HIPCHK(hipMemsetAsync(phd.tdbg.p, 0, 24 * 8, s));
@@ -4402,7 +4327,7 @@ struct Ctx {
   }
 
   int device_update_phi(const std::vector<unsigned char>& mask, int nidx) {
-    if (phi_mode == 0 || (debug & (524288 | 64))) return -1;   // bit 19: host update_phi; bit 6: host pools
+    if (phi_mode == 0 || (debug & kDbgPhiOnHost)) return -1;
     if (phi_mode == 3) {                                  // automatic: by the update's size
       int64_t T0 = 0;
       for (int k = 0; k < K; ++k) T0 += mask[k] && h_counts[k] != 0;
@@ -4456,7 +4381,7 @@ struct Ctx {
       }
       HIPCHK(hipStreamSynchronize(stream));
       const int st = PhiOutView(out, L).status();
-      if (first && fast && phd.tdbg.p && std::getenv("HDPM_PHI_TIMING")) {
+      if (first && fast && phd.tdbg.p && sw::get<sw::PHI_TIMING>()) {
         unsigned long long m[24];
         HIPCHK(hipMemcpy(m, phd.tdbg.p, sizeof(m), hipMemcpyDeviceToHost));
         std::string line = "[phi2 us]";
@@ -4467,7 +4392,7 @@ struct Ctx {
         }
         std::fprintf(stderr, "%s\n", line.c_str());
       }
-      if (first && std::getenv("HDPM_PHI_TRACE"))
+      if (first && sw::get<sw::PHI_TRACE>())
         std::fprintf(stderr, "[phi] T %d nw %d tW %d fast_ok %d gs %d G %d min_count %d tree_min %d fast %d tree %d status %d\n",
                      T, pl.nw, pl.tW, (int)pl.fast_ok, pl.gs, pl.G, min_count, phd.tree_min_count, (int)fast,
                      (int)phi_tree_for(pl, min_count), st);
@@ -4478,7 +4403,7 @@ struct Ctx {
     stats.phi_device_last_status = status;
     const int64_t cons = res.cons();
     const uint64_t target = rng.pos + (uint64_t)cons;
-    if ((debug & 2) && !fast) {
+    if ((debug & HDPM_DBG_PHASE_TIMES) && !fast) {
       std::vector<int64_t> dts(T);
       HIPCHK(hipMemcpy(dts.data(), phd.dts.p, (size_t)T * 8, hipMemcpyDeviceToHost));
       std::vector<int> F((size_t)T * pl.S * pl.Wc);
@@ -4557,7 +4482,7 @@ struct Ctx {
   int committed_gen = 0;               // the fast update update_phi committed last (0: another)
   bool phi_chain = true;               // HDPM_PHI_CHAIN=0: no chained updates
   hipEvent_t ev_phd_free = nullptr;    // the last device use of phd's buffers on `stream` is done
-  bool dspec_on() const { return phi_dev_for((int64_t)K * d) && !(debug & (524288 | 64 | 128)); }
+  bool dspec_on() const { return phi_dev_for((int64_t)K * d) && !(debug & (kDbgPhiOnHost | HDPM_DBG_NO_SPEC_PHI)); }
   void phd_release(hipStream_t s) {
     if (!ev_phd_free) HIPCHK(hipEventCreateWithFlags(&ev_phd_free, hipEventDisableTiming));
     HIPCHK(hipEventRecord(ev_phd_free, s));
@@ -4617,7 +4542,7 @@ struct Ctx {
     bool fast = false;
     const PhiPlan pf = fast_plan(K, false, min_count, &fast);
     const PhiPlan pl = fast ? pf : phi_plan(K);
-    if (std::getenv("HDPM_PHI_TRACE"))
+    if (sw::get<sw::PHI_TRACE>())
       std::fprintf(stderr, "[phi dspec launch] T %d p_rej %.4f nw %d tW %d fast_ok %d gs %d G %d min_count %d tree_min %d fast %d\n",
                    K, phd.p_rej, pf.nw, pf.tW, (int)pf.fast_ok, pf.gs, pf.G, min_count, phd.tree_min_count, (int)fast);
     if (!pl.ok) return;
@@ -4658,12 +4583,8 @@ struct Ctx {
   // dspec completed.  pipe_go makes it the next iteration's speculation (dspec_promote).
   void dnext_launch(int m) {
     dnext.ran = false;
-    static const bool env_off = [] {
-      const char* e = std::getenv("HDPM_PHI_CHAIN");
-      return e && e[0] == '0';
-    }();
-    if (!phi_chain || env_off || !dspec.ran || !dspec.fast || !dspec.inflight || dspec.gen != phd.gen ||
-        phd.fast_backoff > 0 || K <= 0)
+    if (!sw::get<sw::PHI_CHAIN>() || !phi_chain || !dspec.ran || !dspec.fast || !dspec.inflight ||
+        dspec.gen != phd.gen || phd.fast_backoff > 0 || K <= 0)
       return;
     const PhiPlan pl = phi_plan(K, false, kPhiFastSd / kPhiSd);
     if (!pl.ok || !phi_fast(pl)) return;
@@ -4724,7 +4645,7 @@ struct Ctx {
     const PhiOutView res(dspec.out, phi_out_layout(T, d));
     const int status = res.status();
     if (dspec.fast && status != kPhiOk) stats.phi_fast_handbacks++;
-    if (std::getenv("HDPM_PHI_TRACE"))
+    if (sw::get<sw::PHI_TRACE>())
       std::fprintf(stderr, "[phi dspec] T %d fast %d status %d\n", T, (int)dspec.fast, status);
     stats.phi_device_last_status = status;
     const int64_t cons = res.cons();
@@ -4778,7 +4699,8 @@ struct Ctx {
   int device_update_phi_sm(int T, const int* cnt, const unsigned* freq, const double* sig_in, uint8_t* cen,
                            double* sig) {
     // (automatic mode: split-merge's updates stay on the host job)
-    if (phi_mode == 0 || phi_mode == 3 || (debug & (524288 | 64)) || T <= 0 || d > 2048 || !glibc_selfcheck()) return -1;
+    if (phi_mode == 0 || phi_mode == 3 || (debug & kDbgPhiOnHost) || T <= 0 || d > 2048 || !glibc_selfcheck())
+      return -1;
     rng_sync();
     // a drift past the window (a merged or freshly split cluster can reject far more attempts
     // than the chain's updates; nothing was consumed) is retried with a wider window
@@ -4826,7 +4748,7 @@ struct Ctx {
     const uint64_t target = rng.pos + (uint64_t)cons;
     if (status != kPhiOk || cons <= 0 || !can_adopt(*W, target)) {
       if (status == kPhiOk) stats.phi_device_last_status = -1;
-      if (std::getenv("HDPM_PHI_TRACE"))
+      if (sw::get<sw::PHI_TRACE>())
         std::fprintf(stderr, "[phi sm] T %d items %lld need %lld nw %d p_rej %.4f status %d cons %lld counts %d %d\n", T,
                      (long long)items, (long long)pl.need, pl.nw, phd.p_rej_sm, status, (long long)cons, cnt[0],
                      T > 1 ? cnt[1] : -1);
@@ -4867,7 +4789,7 @@ struct Ctx {
     // speculation of the sweep just done (spec_launch), for the full update only
     const bool use_spec = nidx == 0 && spec.ran && spec.lv == labels_version && spec.moves >= 0 &&
                           spec.pos == rng.pos && spec.epoch == rng.epoch && sa.n > 0 && sa.start.pos == rng.pos &&
-                          !(debug & 128);
+                          !(debug & HDPM_DBG_NO_SPEC_PHI);
     spec.ran = false;
     // the device speculation of the sweep just done (dspec_launch)
     const bool use_dspec = nidx == 0 && dspec.ran && dspec.lv == labels_version && dspec.moves == 0 &&
@@ -5005,13 +4927,13 @@ struct Ctx {
   // ------------------------------------------------------------------ loglik
   int compute_loglikelihood(double* out) {
     if (!have_state) { err = "no state"; return kArg; }
-    if (dev_ll_version == labels_version && !tables_dirty && !(debug & 4)) {
+    if (dev_ll_version == labels_version && !tables_dirty && !(debug & HDPM_DBG_LL_PER_POINT)) {
       // the full device update_phi of these labels summed the regrouped terms (phi.hip)
       *out = dev_ll;
       return kOk;
     }
     if (tables_dirty) upload_clusters();
-    if (freq_version == labels_version && stage_full && !(debug & 4)) {
+    if (freq_version == labels_version && stage_full && !(debug & HDPM_DBG_LL_PER_POINT)) {
       // the labels have not moved since the last full histogram: the sum over points
       // regroups exactly into per-(cluster, attribute) match / mismatch counts times the
       // dhamming table values (the tables of the last full upload, still in h_stage)
@@ -5150,11 +5072,11 @@ int Ctx::iteration(const hdpm_chain_params* p, int iter, int* idx_1_sm, int* acc
   // committed and its log-likelihood summed (both off the host's critical path, which is the
   // chain of update_phi draws): when this iteration is a lone Neal-8 sweep whose update
   // came from the speculation and whose log-likelihood needs no device work
-  const bool early = n8 && !sm_now && next_n8 && iter % 1000 != 0 && !(debug & 2097152);
+  const bool early = n8 && !sm_now && next_n8 && iter % 1000 != 0 && !(debug & HDPM_DBG_COMMIT_FIRST);
   if (!n8) cancel_ahead();
   if (n8) {                                              // la:94-103
     // the next sweep may be enqueued while this one's update is drawn (pre_enqueue)
-    deep_ok = early && launch_next && !(debug & 4194304);
+    deep_ok = early && launch_next && !(debug & HDPM_DBG_NO_PIPE);
     record_now = labels_out != nullptr;
     st = neal8_sweep(p->m);
     deep_ok = false;
@@ -5181,7 +5103,8 @@ int Ctx::iteration(const hdpm_chain_params* p, int iter, int* idx_1_sm, int* acc
     else pre_release();
   }
   if (!have_state) return kArg;                          // (a go the host could not follow: pipe_desync)
-  if (!prepared && early && commit_later.active && freq_version == labels_version && !(debug & 4) && !tables_dirty) {
+  if (!prepared && early && commit_later.active && freq_version == labels_version && !(debug & HDPM_DBG_LL_PER_POINT) &&
+      !tables_dirty) {
     prepare_next_sweep(p->m, launch_next);               // spec_launch, flush_commit, round 0
     prepared = true;
   }
@@ -5212,7 +5135,7 @@ int Ctx::iteration(const hdpm_chain_params* p, int iter, int* idx_1_sm, int* acc
   }
   if (prepared && ahead.active && host_spec()) phi_lookahead();
   mark("ahead");
-  if ((debug & 32) && trace.size() > 1) {
+  if ((debug & HDPM_DBG_TIMELINE) && trace.size() > 1) {
     if (trace_alloc0 < 0) trace_alloc0 = g_dev_allocs.load();
     for (size_t k = 1; k < trace.size(); ++k) {
       const double us = std::chrono::duration<double, std::micro>(trace[k].second - trace[k - 1].second).count();
@@ -5232,7 +5155,7 @@ int Ctx::iteration(const hdpm_chain_params* p, int iter, int* idx_1_sm, int* acc
     }
     trace_iters++;
   }
-  if ((debug & 2) && trace.size() > 1) {
+  if ((debug & HDPM_DBG_PHASE_TIMES) && trace.size() > 1) {
     std::string line = "[iter]";
     for (size_t k = 1; k < trace.size(); ++k) {
       char buf[96];
@@ -5399,12 +5322,13 @@ int hdpm_ctx_create(int32_t device, hdpm_ctx** out) {
   // lowest: a window's generation (~1 ms per 16 sweeps of draws) then takes the CUs the
   // sweep leaves (HDPM_STREAM_PRIO=0: default priorities)
   int prio_lo = 0, prio_hi = 0;
-  const char* sp = std::getenv("HDPM_STREAM_PRIO");
-  if (!(sp && sp[0] == '0') && hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi) != hipSuccess) prio_lo = prio_hi = 0;
+  const char sp = hdpm::sw::stream_prio();
+  if (sp != '0' && hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi) != hipSuccess) prio_lo = prio_hi = 0;
   // (testing, HDPM_STREAM_PRIO=2: the sweep's stream at the generator's priority, the device
   // update_phi's above it)
-  const int prio_sweep = (sp && sp[0] == '2') ? prio_lo : prio_hi;
-  if (std::getenv("HDPM_PHI_TRACE")) std::fprintf(stderr, "[streams] priorities %d..%d sweep %d\n", prio_lo, prio_hi, prio_sweep);
+  const int prio_sweep = sp == '2' ? prio_lo : prio_hi;
+  if (hdpm::sw::get<hdpm::sw::PHI_TRACE>())
+    std::fprintf(stderr, "[streams] priorities %d..%d sweep %d\n", prio_lo, prio_hi, prio_sweep);
   if (hipSetDevice(device) != hipSuccess ||
       hipStreamCreateWithPriority(&c->stream, hipStreamNonBlocking, prio_sweep) != hipSuccess) {
     delete c;

@@ -924,12 +924,7 @@ static int wide_grid(F kern, size_t lds, int want) {
   int per = 0;
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, kern, kWideThreads, lds) != hipSuccess || per <= 0) per = 1;
   if (want > 0) per = std::min(per, want);
-  // HDPM_WIDE_WGS: workgroups per CU (A/B of the persistent grid)
-  static const int ovr = [] {
-    const char* e = std::getenv("HDPM_WIDE_WGS");
-    return e ? std::atoi(e) : 0;
-  }();
-  if (ovr > 0 && ovr <= 32) per = ovr;
+  if (const int ovr = sw::get<sw::WIDE_WGS>()) per = ovr;
   return cus * per;
 }
 
@@ -2942,7 +2937,7 @@ __global__ __launch_bounds__(kFpThreads) void k_resolve_fp(ResolveArgs a) {
     int cls = 0, tgt = own, pick = -1, co = 0, ct = 0;   // cls: 0 stay, 1 case-1 move to tgt, 2 stop
     // The first round's guess: the snapshot draws' outcomes in the chunk-start state (any guess
     // converges to the same fixed point; a right one does so in one round instead of two;
-    // debug bit 26 starts from "stay")
+    // HDPM_DBG_FP_FROM_STAY starts from "stay")
     if (in && struct0 && sp >= 0 && !(a.debug_fp & 1)) {
       const bool single0 = st.cnt[own] == 1;
       if (sp < K) {
@@ -3563,12 +3558,7 @@ static hipError_t launch_prepass_w(const PrepassArgs& a, int nblocks, hipStream_
       // (the same number of chunks for every workgroup -- 875 workgroups x 5 chunks at C4 instead of
       // 1,024 x 4-5 -- measured 54 against 47 us: the kernel wants every resident wave)
       const int grid = std::min(nchunks, wide_grid(kern, lds, a.wide_per_cu));
-      // HDPM_WIDE_CLAIM=1: chunks claimed from a counter (A/B; see k_prepass_wide)
-      static const int claim = [] {
-        const char* e = std::getenv("HDPM_WIDE_CLAIM");
-        return e ? std::atoi(e) : 0;
-      }();
-      HDPM_LAUNCH(kern, dim3(grid), dim3(kWideThreads), lds, s, a, nchunks, claim);
+      HDPM_LAUNCH(kern, dim3(grid), dim3(kWideThreads), lds, s, a, nchunks, sw::get<sw::WIDE_CLAIM>());
       return hipGetLastError();
     };
     if constexpr (WB <= 2) {
@@ -4123,18 +4113,10 @@ hipError_t launch_exact_rows(const PrepassArgs& a0, int nblocks, hipStream_t s, 
   const dim3 g(a.exact_grid > 0 ? a.exact_grid : std::min(nblocks * 4, 1024)), b(kExactWgThreads);
   const size_t mlds = exact_mass_lds_bytes(a.K, a.m, a.d, a.nq * 16);
   const size_t llds = (size_t)a.K * (2 * a.d * 8 + a.nq * 16);
-  // HDPM_EXACT_MASS=1: the wave-per-point kernel for these sweeps too (A/B)
-  static const bool force_mass = [] {
-    const char* e = std::getenv("HDPM_EXACT_MASS");
-    return e && std::atoi(e) == 1;
-  }();
-  // HDPM_EXACT_LANES=1: the thread-per-point kernel with compare / select (A/B of the level tables)
-  static const bool force_lanes = [] {
-    const char* e = std::getenv("HDPM_EXACT_LANES");
-    return e && std::atoi(e) == 1;
-  }();
+  // HDPM_OPT_EXACT_KERNEL 1: the wave-per-point kernel for these sweeps too; 2: the thread-per-point
+  // kernel with compare / select (A/B of the level tables)
   const size_t vlds = exact_lv_lds_bytes(a.K, a.nq, a.mmax);
-  const bool want_mass = force_mass || a.exact_pref == 1, want_lanes = force_lanes || a.exact_pref == 2;
+  const bool want_mass = a.exact_pref == 1, want_lanes = a.exact_pref == 2;
   // (with snapshot draws when spec is set: k_snap_draws behind the rows)
   if (a.exact_scan && (!a.spec || a.spec_lv) && !a.exact_wave && a.nq <= kLanesMaxNq && a.K <= kWave && a.mmax >= 1 &&
       vlds <= 120 * 1024 && !want_mass && !want_lanes) {
@@ -4149,11 +4131,8 @@ hipError_t launch_exact_rows(const PrepassArgs& a0, int nblocks, hipStream_t s, 
     return launch_snap_draws(an, s);
   }
   if (a.exact_scan && !a.exact_wave && E <= kWave && mlds <= 96 * 1024) {
-    static const int mstatic = [] {
-      const char* e = std::getenv("HDPM_MASS_STATIC");
-      return e ? std::atoi(e) : 0;
-    }();
-    HDPM_LAUNCH(k_exact_rows_mass, dim3(mass_grid(mlds)), dim3(kWave * kMassWaves), mlds, s, a, mstatic);
+    HDPM_LAUNCH(k_exact_rows_mass, dim3(mass_grid(mlds)), dim3(kWave * kMassWaves), mlds, s, a,
+                sw::get<sw::MASS_STATIC>());
     if (path) *path = 1;
     return hipGetLastError();
   }
@@ -4255,15 +4234,8 @@ hipError_t warm_launch_kernels(const PrepassArgs& pa0, const ResolveArgs& ra0, c
   ra.gate = zero;
   ra.raw_ptr = zero_ptr;
   const dim3 one(1);
-  // HDPM_WARM_SYNC=1 (diagnosis): synchronise after every launch and name it on stderr
-  static const bool wsync = [] {
-    const char* e = std::getenv("HDPM_WARM_SYNC");
-    return e && std::atoi(e) == 1;
-  }();
-  static const int wmask = [] {
-    const char* e = std::getenv("HDPM_WARM_MASK");
-    return e ? (int)std::strtol(e, nullptr, 0) : -1;
-  }();
+  const bool wsync = sw::get<sw::WARM_SYNC>();
+  const int wmask = sw::warm_mask();
   int k = 0;
   auto step = [&](const char* name) -> hipError_t {
     hipError_t e = hipGetLastError();

@@ -7,18 +7,14 @@
 #include <cstdio>
 #include <cstdlib>
 
+#include "switches.hpp"
+
 namespace hdpm {
 
 // Diagnosis (HDPM_SYNC_EACH=1): every kernel launch of the engine is followed by a stream
 // synchronisation and its name and status on stderr, so a device fault is pinned on the
 // kernel that raised it (the next launch would otherwise report it).
-inline bool sync_each() {
-  static const bool on = [] {
-    const char* e = std::getenv("HDPM_SYNC_EACH");
-    return e && std::atoi(e) == 1;
-  }();
-  return on;
-}
+inline bool sync_each() { return sw::get<sw::SYNC_EACH>(); }
 inline void sync_report(const char* name, hipStream_t s) {
   hipError_t e = hipGetLastError();
   if (e == hipSuccess) e = hipStreamSynchronize(s);

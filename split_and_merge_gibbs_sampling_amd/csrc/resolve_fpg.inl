@@ -240,7 +240,7 @@ __global__ __launch_bounds__(kFpThreads) void k_resolve_fpg(ResolveArgs a) {
   FpgShared* X = (FpgShared*)(smem + ((resolve_fp_lds_bytes(a.lcap, a.m) + 15) & ~(size_t)15));
   const fpg::Lay L = fpg::lay(a.fpg_buf, G);
   long long tp[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  // debug bit 1 profile (workgroup 0): [2] ticks in grid barriers, [3] in the rounds, [4] in
+  // HDPM_DBG_PHASE_TIMES profile (workgroup 0): [2] ticks in grid barriers, [3] in the rounds, [4] in
   // the drift / re-test / commit phase; tsub[0] windows
   const bool prof = a.prof != nullptr && g == 0;
   if (prof) tp[0] = wall_clock64();

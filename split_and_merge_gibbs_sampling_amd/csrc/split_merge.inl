@@ -19,13 +19,7 @@ hipError_t launch_phi2(const PhiArgs& a, hipStream_t s, hipEvent_t before_values
 
 // HDPM_SM_WIDE=0: the one-workgroup restricted scan only (A/B of k_sm_scan_wide, the default:
 // 13.5 against 80 us per C4 scan, profiles/r05/split_merge/wide/)
-static bool sm_wide_on() {
-  static const bool on = [] {
-    const char* e = std::getenv("HDPM_SM_WIDE");
-    return !(e && e[0] == '0');
-  }();
-  return on;
-}
+static bool sm_wide_on() { return sw::get<sw::SM_WIDE>(); }
 
 // A host copy of internal_state (cfh:32-63): labels, parameters, sizes.
 struct HState {
@@ -327,7 +321,7 @@ static int hupdate_phi_pair(Ctx* c, HState& s, int ka, const Freq& Fa, int kb, c
     const Freq* fs[2] = {ka <= kb ? &Fa : &Fb, ka <= kb ? &Fb : &Fa};
     if (dupdate_phi_sm(c, s, ks, fs, ka == kb ? 1 : 2) == kOk) return kOk;
   }
-  if (c->d < 128 || (c->debug & 128)) {
+  if (c->d < 128 || (c->debug & HDPM_DBG_NO_SPEC_PHI)) {
     int st = ka <= kb ? hupdate_phi_one(c, s, ka, Fa) : hupdate_phi_one(c, s, kb, Fb);
     if (st) return st;
     if (ka != kb) st = ka < kb ? hupdate_phi_one(c, s, kb, Fb) : hupdate_phi_one(c, s, ka, Fa);
@@ -468,7 +462,9 @@ static int sm_chain(Ctx* c, SmWork& W, const std::vector<int>& S, HState& s, int
   const int c1 = s.c[i1], c2 = s.c[i2];
   const int nS = (int)S.size(), d = c->d, mm = c->mmax;
   if (c->sm_chain_mode == 0 || t < 1 || t > 64 || nS < 1 || c1 == c2) return -1;
-  if (c->phi_mode == 0 || (c->debug & (524288 | 64 | 65536)) || d > 2048 || !Ctx::glibc_selfcheck()) return -1;
+  if (c->phi_mode == 0 || (c->debug & (Ctx::kDbgPhiOnHost | HDPM_DBG_SM_HOST_DRAWS)) || d > 2048 ||
+      !Ctx::glibc_selfcheck())
+    return -1;
   if (!sm_ll_lds_fits(d, c->nq)) return -1;
   bool fast = false;
   const Ctx::PhiPlan pf = c->fast_plan(1, true, 16, &fast);
@@ -722,7 +718,7 @@ static int sm_chain(Ctx* c, SmWork& W, const std::vector<int>& S, HState& s, int
     c->stats.phi_fast_handbacks++;
     if (stk == kPhiShort || stk == kPhiWindow) Ctx::PhiDevice::widen(phd.p_rej_sm, 0.9);
   }
-  if (std::getenv("HDPM_PHI_TRACE"))
+  if (sw::get<sw::PHI_TRACE>())
     std::fprintf(stderr, "[sm chain] t %d nS %d: scan %d %s (update status %d)\n", t, nS, kf,
                  !scan_kf ? "off" : (uf & 1) ? "ran, second update handed back" : "ran, update handed back", stk);
   uint64_t pos;
@@ -779,8 +775,8 @@ static int restricted_gibbs(Ctx* c, const std::vector<int>& S, HState& s, int i1
     }
   }
   // large scans take their |S| draws from the device windows (no host generation and copy;
-  // the host stream adopts the state after them); debug bit 16 draws them on the host
-  const bool dev_draws = nS >= 4096 && !(c->debug & 65536);
+  // the host stream adopts the state after them); HDPM_DBG_SM_HOST_DRAWS draws them on the host
+  const bool dev_draws = nS >= 4096 && !(c->debug & HDPM_DBG_SM_HOST_DRAWS);
   // the whole sampler as one device chain where it applies (sm_chain); the host continues
   // from the first step the chain did not finish
   int iter0 = 0, at_phi = 0;

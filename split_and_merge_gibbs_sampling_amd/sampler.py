@@ -12,7 +12,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import HdpmError, ptr
+from ._lib import Debug, HdpmError, ptr  # noqa: F401
 
 
 def _i32(a):

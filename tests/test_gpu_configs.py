@@ -19,6 +19,8 @@ import os
 import numpy as np
 import pytest
 
+from split_and_merge_gibbs_sampling_amd import Debug
+
 pytestmark = pytest.mark.gpu
 
 RTOL = 1e-10
@@ -151,10 +153,10 @@ def test_c4_full_size_neal8_and_split_merge(hd, oracle):
 
 @pytest.mark.timeout(900)
 @pytest.mark.parametrize("L", [1, 20])
-# 0: the fixed-point resolver (k_resolve_fp); 4096: the one-wave LIST resolver without block
-# mode; 8388608 (bit 23): the one-wave resolvers with block mode after many exact decisions;
-# 1073741824 (bit 30): the device-wide fixed-point resolver (k_resolve_fpg) for every launch
-@pytest.mark.parametrize("debug", [0, 4096, 8388608, 1073741824])
+# 0: the fixed-point resolver (k_resolve_fp); NO_BLOCK_MODE: the one-wave LIST resolver without
+# block mode; ONE_WAVE_RESOLVER: the one-wave resolvers with block mode after many exact decisions;
+# FPG_ALWAYS: the device-wide fixed-point resolver (k_resolve_fpg) for every launch
+@pytest.mark.parametrize("debug", [0, int(Debug.NO_BLOCK_MODE), int(Debug.ONE_WAVE_RESOLVER), int(Debug.FPG_ALWAYS)])
 def test_c2_full_size_unconverged_starts(hd, oracle, L, debug):
     """C2: N = 10,000, D = 32, binary, from one cluster (L = 1) or a random assignment to 20
     labels (la:31-43, the scripts' L = 20): far from the posterior, points move every sweep
@@ -208,7 +210,7 @@ def test_c5_full_size_random20_start(hd, oracle, lat):
 
 
 @pytest.mark.timeout(1200)
-# mode "": the default path; "nopipe": debug bit 22 (no sweep enqueued ahead of the update's
+# mode "": the default path; "nopipe": Debug.NO_PIPE (no sweep enqueued ahead of the update's
 # go -- the same chain without the device-gated pipeline); "gateoff": the enqueued sweep's wait
 # kernel gives up after 1 us with no host-side check, so nearly every enqueued sweep is gated
 # off on the device and re-run ungated by the engine (its recovery path)
@@ -237,7 +239,7 @@ def test_bench_path_iterations_api(hd, oracle, name, warm, timed, mode):
     sweep) -- as launcher.cpp:85-132 would leave them."""
     ds, eng, ost, rng, pc, ps = start(hd, oracle, name, seed=11)
     if mode == "nopipe":
-        eng.set_debug(4194304)
+        eng.set_debug(Debug.NO_PIPE)
     elif mode == "gateoff":
         eng.set_pipe_wait_us(-1.0)
     elif mode == "phidev":
@@ -314,7 +316,7 @@ def test_c2_device_wide_resolver_gives_up_and_recovers(hd, oracle, fail_at, wait
     eng = hd.Engine(0)
     eng.set_data(ds.codes, ds.attrisize, ds.gamma, ds.v, ds.w)
     eng.set_seed(4)
-    eng.set_debug(1073741824)
+    eng.set_debug(Debug.FPG_ALWAYS)
     if fail_at:
         eng.set_fpg_fail_at(fail_at)
     if wait_us:

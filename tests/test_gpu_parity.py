@@ -7,10 +7,17 @@ import os
 import numpy as np
 import pytest
 
+from split_and_merge_gibbs_sampling_amd import Debug as D
+
 pytestmark = pytest.mark.gpu
 
 G = os.path.join(os.path.dirname(__file__), "golden")
 RTOL = 1e-10
+
+
+def modes(*debug):
+    """hdpm_set_debug modes for a parametrization, as plain ints (the test ids stay numbers)."""
+    return [int(v) for v in debug]
 
 
 @pytest.fixture(scope="module")
@@ -96,10 +103,10 @@ def sweep_case(hd, oracle, ds, c, cen, sig, P, seed, m=3, debug=0, sweeps=1, phi
     return stats
 
 
-# debug 0: default (snapshot speculation in the exact-rows kernel), 1: every point on the
-# exact path in the resolver, 8: no speculation (the resolver decides every listed point)
-# 8192: the resolver's block mode for every launch (parallel decisions, serial walk)
-@pytest.mark.parametrize("debug", [0, 1, 8, 2048, 8192])
+# debug 0: default (snapshot speculation in the exact-rows kernel), EXACT_ALL: every point on the
+# exact path in the resolver, NO_SNAPSHOT: no speculation (the resolver decides every listed point)
+# BLOCK_MODE_ALWAYS: the resolver's block mode for every launch (parallel decisions, serial walk)
+@pytest.mark.parametrize("debug", modes(0, D.EXACT_ALL, D.NO_SNAPSHOT, D.EXACT_WAVE, D.BLOCK_MODE_ALWAYS))
 def test_zoo_single_sweeps_from_truth(hd, oracle, zoo, debug):
     cen, sig = random_params(zoo, 7, 3)
     stats = sweep_case(hd, oracle, zoo, zoo.truth, cen, sig, zoo.n * 3, seed=17, debug=debug, sweeps=3)
@@ -113,7 +120,7 @@ def test_zoo_sweeps_with_update_phi_all_singletons(hd, oracle, zoo):
     sweep_case(hd, oracle, zoo, c, cen, sig, zoo.n * 3, seed=23, sweeps=4, phi=True)
 
 
-@pytest.mark.parametrize("debug", [0, 8, 8192])
+@pytest.mark.parametrize("debug", modes(0, D.NO_SNAPSHOT, D.BLOCK_MODE_ALWAYS))
 def test_zoo_sweeps_with_update_phi_one_cluster(hd, oracle, zoo, debug):
     # L = 1: the first sweeps create clusters (case 3 -> device restarts)
     c = np.zeros(zoo.n, np.int32)
@@ -122,11 +129,13 @@ def test_zoo_sweeps_with_update_phi_one_cluster(hd, oracle, zoo, debug):
     assert stats["restarts"] > 0
 
 
-# 16: recount the frequency tables every update_phi; 128: no speculative update_phi;
-# 2048: exact rows one wave per point; 4096: no block mode in the resolver; 8192: block mode
-# for every launch
+# RECOUNT: recount the frequency tables every update_phi; NO_SPEC_PHI: no speculative update_phi;
+# EXACT_WAVE: exact rows one wave per point; NO_BLOCK_MODE: no block mode in the resolver;
+# BLOCK_MODE_ALWAYS: block mode for every launch
 @pytest.mark.parametrize("phi_device", [False, True])
-@pytest.mark.parametrize("debug", [0, 1, 8, 16, 128, 2048, 2048 | 1, 4096, 8192, 8192 | 8, 262144])
+@pytest.mark.parametrize("debug", modes(0, D.EXACT_ALL, D.NO_SNAPSHOT, D.RECOUNT, D.NO_SPEC_PHI, D.EXACT_WAVE,
+                                        D.EXACT_WAVE | D.EXACT_ALL, D.NO_BLOCK_MODE, D.BLOCK_MODE_ALWAYS,
+                                        D.BLOCK_MODE_ALWAYS | D.NO_SNAPSHOT, D.MARGIN_ONLY))
 def test_synthetic_sweeps_with_update_phi(hd, oracle, debug, phi_device):
     ds = synth(6000, 32, 8, 2, seed=3)
     cen, sig = random_params(ds, 8, 7)
@@ -140,7 +149,8 @@ def test_speculative_update_phi(hd, oracle):
     # ran during the sweep; every step is compared with the oracle.
     ds = synth(4000, 64, 6, 4, seed=9)
     cen, sig = random_params(ds, 6, 11)
-    stats = sweep_case(hd, oracle, ds, ds.truth, cen, sig, ds.n * 3, seed=41, sweeps=8, phi=True, debug=524288)
+    stats = sweep_case(hd, oracle, ds, ds.truth, cen, sig, ds.n * 3, seed=41, sweeps=8, phi=True,
+                       debug=D.PHI_HOST)
     assert stats["phi_spec_runs"] >= 6
     assert stats["phi_spec_clusters"] > 0
 
@@ -149,7 +159,7 @@ def test_speculative_update_phi(hd, oracle):
 # after it against the oracle, on shapes with one and several attribute classes, binary and
 # many-level attributes, wide rows; and that the device path ran (no silent host fallback).
 # path: "fast" (launch_phi2, the default where every pick is fixed), "trees" (the general
-# kernels' composition trees), "walks" (debug bit 27: the per-start-drift walks, k_phi_cwalk)
+# kernels' composition trees), "walks" (PHI_WALKS: the per-start-drift walks, k_phi_cwalk)
 @pytest.mark.parametrize("path", ["fast", "trees", "walks"])
 @pytest.mark.parametrize("shape", ["c5_like", "mixed", "binary", "wide", "zoo"])
 def test_device_update_phi(hd, oracle, zoo, shape, path):
@@ -160,7 +170,8 @@ def test_device_update_phi(hd, oracle, zoo, shape, path):
                  "binary": (synth(6000, 32, 8, 2, seed=7), 8), "wide": (synth(2500, 784, 6, 6, seed=8), 6)}[shape]
     cen, sig = random_params(ds, K, 13)
     stats = sweep_case(hd, oracle, ds, ds.truth, cen, sig, ds.n * 3, seed=43, sweeps=4, phi=True,
-                       phi_device=True if path == "fast" else "general", debug=134217728 if path == "walks" else 0)
+                       phi_device=True if path == "fast" else "general",
+                       debug=D.PHI_WALKS if path == "walks" else 0)
     phis = {k: v for k, v in stats.items() if "phi" in k}
     assert stats["phi_device_calls"] >= 2, phis
     if path == "fast":
@@ -308,7 +319,7 @@ def test_compute_loglikelihood_matches_sequential_sum(hd, oracle, zoo):
 
 def test_compute_loglikelihood_from_counts_after_update_phi(hd, oracle):
     # after a sweep + update_phi the engine regroups the sum into per-(cluster, attribute)
-    # match counts; it must agree with the per-point kernel (debug bit 2) and the oracle
+    # match counts; it must agree with the per-point kernel (LL_PER_POINT) and the oracle
     ds = synth(30000, 96, 6, (2, 5), seed=8)
     cen, sig = random_params(ds, 6, 11)
     eng = make_engine(hd, ds)
@@ -319,7 +330,7 @@ def test_compute_loglikelihood_from_counts_after_update_phi(hd, oracle):
         eng.neal8_sweep(2)
         eng.update_phi()
         fast = eng.compute_loglikelihood()
-        eng.set_debug(4)
+        eng.set_debug(D.LL_PER_POINT)
         slow = eng.compute_loglikelihood()
         eng.set_debug(0)
         c, cen2, sig2 = eng.get_state()
@@ -366,8 +377,8 @@ def test_restricted_gibbs_large_clusters(hd, oracle):
 
 
 # d >= 128: the scans' update_phi goes through the engine's pipelined update_phi job
-# (split_merge.inl hupdate_phi_job); debug 128 keeps the one-pass path
-@pytest.mark.parametrize("debug", [0, 128])
+# (split_merge.inl hupdate_phi_job); NO_SPEC_PHI keeps the one-pass path
+@pytest.mark.parametrize("debug", modes(0, D.NO_SPEC_PHI))
 def test_restricted_gibbs_wide_update_phi(hd, oracle, debug):
     ds = synth(3000, 200, 4, 6, seed=39)
     cen, sig = random_params(ds, 4, 12)
@@ -764,8 +775,8 @@ def test_device_pool_matches_oracle_zoo(hd, oracle, zoo, pre):
     assert st["pool_device_calls"] == 1
 
 
-# c5_large: 200k entries (~1,560 chunks / 25 groups of the segment parse, k_pool_seg*); serial_parse: debug
-# bit 28, the entry starts by the sequential host walk over the device's acceptance tables
+# c5_large: 200k entries (~1,560 chunks / 25 groups of the segment parse, k_pool_seg*); serial_parse:
+# POOL_SERIAL_PARSE, the entry starts by the sequential host walk over the device's acceptance tables
 @pytest.mark.parametrize("case", ["mixed_levels", "odd_d_bc", "c5_like", "c5_large", "serial_parse", "host_forced"])
 def test_device_pool_matches_oracle_synthetic(hd, oracle, case):
     if case == "mixed_levels":
@@ -781,7 +792,7 @@ def test_device_pool_matches_oracle_synthetic(hd, oracle, case):
         v, w, P = np.full(128, 6.0), np.full(128, 0.25), 30000   # ~14M draws: multi-workgroup slice
         if case == "c5_large":
             P = 200_000
-    debug = {"host_forced": 64, "serial_parse": 268435456}.get(case, 0)
+    debug = {"host_forced": D.HOST_POOL, "serial_parse": D.POOL_SERIAL_PARSE}.get(case, 0)
     st = _pool_case(hd, oracle, ds, v, w, P, 77, 9, debug=debug)
     assert st["pool_device_calls"] == (0 if case == "host_forced" else 1)
     if case != "host_forced":
@@ -915,15 +926,15 @@ def test_pool_heads_binary_and_absent(hd, oracle):
     eng.close()
 
 
-# 1024: full bound records for the latent picks (no heads) on a head-eligible layout
-@pytest.mark.parametrize("debug", [0, 1024, 8192])
+# NO_POOL_HEADS: full bound records for the latent picks (no heads) on a head-eligible layout
+@pytest.mark.parametrize("debug", modes(0, D.NO_POOL_HEADS, D.BLOCK_MODE_ALWAYS))
 def test_c5_like_sweeps_heads_and_records(hd, oracle, debug):
     ds = synth(5000, 128, 8, 4, seed=24)
     cen, sig = random_params(ds, 8, 25)
     sweep_case(hd, oracle, ds, ds.truth, cen, sig, ds.n * 3, seed=43, sweeps=3, phi=True, debug=debug)
 
 
-@pytest.mark.parametrize("debug", [0, 1024])
+@pytest.mark.parametrize("debug", modes(0, D.NO_POOL_HEADS))
 def test_wide_mixed_levels_sweeps_heads_and_records(hd, oracle, debug):
     ds = synth(3000, 200, 6, (2, 6), seed=27)          # Ws = 4, wb = 4 heads
     cen, sig = random_params(ds, 6, 28)
@@ -931,10 +942,11 @@ def test_wide_mixed_levels_sweeps_heads_and_records(hd, oracle, debug):
 
 
 # k_prepass_wide (16-lane group per point) against the oracle on wide layouts, with heads,
-# with full records (1024) and with the generic one-thread-per-point prepass (16384).  The
+# with full records (NO_POOL_HEADS) and with the generic one-thread-per-point prepass
+# (NO_WIDE_PREPASS).  The
 # chain starts from the ground truth with update_phi'd parameters (hdpm_init_chain), so
 # most points are certified by the bounds and the rest take exact rows.
-@pytest.mark.parametrize("debug", [0, 1024, 16384])
+@pytest.mark.parametrize("debug", modes(0, D.NO_POOL_HEADS, D.NO_WIDE_PREPASS))
 @pytest.mark.parametrize("shape", ["c4", "c4_k80", "ws18_binary", "ws5_wb8", "ws5_wb2", "ws20_wb2", "ws16_wb4"])
 def test_wide_prepass_sweeps(hd, oracle, debug, shape):
     if shape == "c4":
@@ -997,9 +1009,9 @@ def test_hig_logspace_chain_large_clusters(hd, oracle):
     np.testing.assert_allclose(res["loglikelihood"], ref["loglikelihood"], rtol=RTOL, atol=0)
 
 
-# Moves over |S| >= 4096 points: the scans draw from the device windows (debug bit 16 keeps
+# Moves over |S| >= 4096 points: the scans draw from the device windows (SM_HOST_DRAWS keeps
 # them on the host); wide rows (d = 160) also take the pipelined update_phi job.
-@pytest.mark.parametrize("debug", [0, 65536])
+@pytest.mark.parametrize("debug", modes(0, D.SM_HOST_DRAWS))
 def test_split_merge_chain_large_moves(hd, oracle, debug):
     ds = synth(10000, 160, 2, 3, seed=42)
     kw = dict(m=3, iterations=6, L=1, c_i=ds.truth, burnin=0, t=3, r=3, neal8=True, split_merge=True)
@@ -1146,8 +1158,8 @@ def test_restricted_gibbs_random_split_of_one_cluster(hd, oracle):
 
 
 # |S| = 24k: several staged chunks of the scan; the draws come from the device generator
-# windows (|S| >= 4096), or from the host stream (debug bit 16)
-@pytest.mark.parametrize("debug", [0, 65536])
+# windows (|S| >= 4096), or from the host stream (SM_HOST_DRAWS)
+@pytest.mark.parametrize("debug", modes(0, D.SM_HOST_DRAWS))
 def test_restricted_gibbs_sizes_beyond_lds_logn(hd, oracle, debug):
     ds = synth(24000, 12, 2, 2, seed=9)
     c = ds.truth.astype(np.int32).copy()
@@ -1173,7 +1185,7 @@ def test_restricted_gibbs_sizes_beyond_lds_logn(hd, oracle, debug):
 
 # wide rows and a large S: device-window draws for the scans, then the pipelined update_phi
 # job fed from the window's prefetched slice (Ctx::fill_stream_from)
-@pytest.mark.parametrize("debug", [0, 65536])
+@pytest.mark.parametrize("debug", modes(0, D.SM_HOST_DRAWS))
 def test_restricted_gibbs_wide_large_device_draws(hd, oracle, debug):
     ds = synth(9000, 160, 2, 4, seed=41)
     c = ds.truth.astype(np.int32).copy()

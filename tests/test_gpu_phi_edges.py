@@ -18,18 +18,18 @@ tests/phi_predict.py: numpy restatements of the reference's decisions on the ora
 never from the device's status word.  Each test asserts its own predicate on those first.
 
 path: "fast" (launch_phi2 first), "trees" (the general kernels' composition trees), "walks"
-(debug bit 27: the per-start-drift walks)."""
+(Debug.PHI_WALKS: the per-start-drift walks)."""
 import numpy as np
 import pytest
 
 import phi_predict as PP
+from split_and_merge_gibbs_sampling_amd import Debug
 
 pytestmark = pytest.mark.gpu
 
 RTOL = 1e-10
 UPDATES = 3
 PATHS = ["fast", "trees", "walks"]
-WALKS_BIT = 134217728
 MIXED = [2, 16, 17, 3, 40, 6, 255, 16, 17]          # both sides of 16 inside one group of 8
 
 
@@ -170,7 +170,7 @@ def replay(hd, ref, path, sd_scale=None, m=3):
     ds = ref["ds"]
     eng = make_engine(hd, ds)
     try:
-        eng.set_debug(WALKS_BIT if path == "walks" else 0)
+        eng.set_debug(Debug.PHI_WALKS if path == "walks" else 0)
         eng.set_phi_device(True, general=path != "fast")
         if sd_scale is not None:
             eng.set_phi_sd_scale(sd_scale)

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import sm_terms_ref as R
+from split_and_merge_gibbs_sampling_amd import Debug
 
 pytestmark = pytest.mark.gpu
 
@@ -184,7 +185,8 @@ def test_large_moves_same_records_on_every_path(hd, oracle, variant):
     """The device chain, the device update_phi, a wide scan that gives up and host draws change
     where the work runs, not one bit of any addend."""
     setup = {"sm_chain": lambda e: e.set_sm_chain(1), "phi_device": lambda e: e.set_phi_device(True),
-             "wide_wait_0": lambda e: e.set_sm_wide_wait_us(0), "host_draws": lambda e: e.set_debug(65536)}[variant]
+             "wide_wait_0": lambda e: e.set_sm_wide_wait_us(0),
+             "host_draws": lambda e: e.set_debug(Debug.SM_HOST_DRAWS)}[variant]
     base = large_default(hd, oracle)
     recs = run_moves(hd, oracle, "large-6000x64", setup)
     assert len(recs) == len(base)

@@ -17,6 +17,8 @@ same status.
 import numpy as np
 import pytest
 
+from split_and_merge_gibbs_sampling_amd import Debug
+
 pytestmark = pytest.mark.gpu
 
 RTOL = 1e-10
@@ -77,11 +79,15 @@ def test_tiny_shapes_chain_matches_oracle(hd, oracle, shape, m, mode):
     assert np.array_equal(res["rng_state"], rng)
 
 
-# debug 33554432 (bit 25): the fixed-point resolver (k_resolve_fp) for every launch, not only
-# after a launch that listed >= 64 points
-# debug 33554432 | 1073741824 (bits 25, 30): the device-wide fixed-point resolver (k_resolve_fpg,
-# a workgroup per 512-point chunk, grid barriers) for every launch
-@pytest.mark.parametrize("debug", [0, 33554432, 33554432 | 1073741824])
+# FP_ALWAYS: the fixed-point resolver (k_resolve_fp) for every launch, not only after a launch
+# that listed >= 64 points
+# FP_ALWAYS | FPG_ALWAYS: the device-wide fixed-point resolver (k_resolve_fpg, a workgroup per
+# 512-point chunk, grid barriers) for every launch
+FP_EVERY = int(Debug.FP_ALWAYS)
+FPG_EVERY = int(Debug.FP_ALWAYS | Debug.FPG_ALWAYS)
+
+
+@pytest.mark.parametrize("debug", [0, FP_EVERY, FPG_EVERY])
 @pytest.mark.parametrize("mode", ["n8", "both"])
 @pytest.mark.parametrize("shape", [(2, 1, 1, 2), (4, 3, 2, 3), (7, 5, 3, 4), (65, 1, 2, 3), (130, 3, 4, (2, 5))],
                          ids=_shape_id)
@@ -118,11 +124,11 @@ def test_tiny_shapes_iteration_api(hd, oracle, shape, mode, debug):
         e.close()
 
 
-@pytest.mark.parametrize("debug", [0, 16, 33554432, 33554432 | 1073741824])
+@pytest.mark.parametrize("debug", [0, int(Debug.RECOUNT), FP_EVERY, FPG_EVERY])
 def test_tiny_shape_random_init_chain(hd, oracle, debug):
     # random L = 5 initial labels on 40 points: clusters vanish (case 2) and appear (cases 3 /
-    # 4) within the same sweeps, at the last point too; carried tables (0), recounts (16), the
-    # fixed-point resolver for every launch (33554432)
+    # 4) within the same sweeps, at the last point too; carried tables (0), recounts (RECOUNT), the
+    # fixed-point resolver for every launch (FP_ALWAYS)
     ds = _data((40, 4, 3, 3))
     iters = 12
     for seed in range(1, 40):

@@ -62,3 +62,17 @@ def test_host_pool_home_domain_choice(tmp_path):
     r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=60)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "host topology ok" in r.stdout
+
+
+def test_environment_switch_table(tmp_path):
+    """csrc/switches.hpp: every kind of HDPM_* switch on unset, "0", "1", "2", "" and "abc", the
+    integer switches' defaults and ranges, and the read time (once per process / live)."""
+    exe = tmp_path / "switches_test"
+    src = os.path.join(HERE, "cpp", "switches_test.cpp")
+    r = subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-o", str(exe), src], capture_output=True, text=True)
+    if r.returncode != 0:
+        pytest.fail(r.stderr)
+    env = {k: v for k, v in os.environ.items() if not k.startswith("HDPM_")}
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=60, env=env)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "switches ok" in r.stdout

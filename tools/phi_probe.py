@@ -1,5 +1,5 @@
 """Diagnostics: one device update_phi after a sweep on a synthetic shape, with the engine's
-[phi] trace (debug bit 1)."""
+[phi] trace (Debug.PHASE_TIMES)."""
 import os, sys
 R = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, R); sys.path.insert(0, os.path.join(R, "tests"))
@@ -23,7 +23,7 @@ e.set_pool(pc, ps)
 e.rng_state = st
 for it in range(3):
     e.neal8_sweep(3)
-    e.set_debug(2)
+    e.set_debug(hd.Debug.PHASE_TIMES)
     e.update_phi()
     e.set_debug(0)
     s = e.stats()

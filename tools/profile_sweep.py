@@ -1,6 +1,6 @@
 """Diagnostics: per-phase resolver timings and prepass precise-pass counts on a config.
 
-Runs a few Neal-8 iterations with debug mode bit 1 (hdpm_set_debug(2)), which makes the
+Runs a few Neal-8 iterations with Debug.PHASE_TIMES (HDPM_DBG_PHASE_TIMES), which makes the
 engine print '[prepass]' and '[resolve]' lines to stderr per resolver launch.
 Usage: python tools/profile_sweep.py [--config c5] [--iters 3]
 """
@@ -28,7 +28,7 @@ def main():
     eng.init_chain(p, c_i=ds.truth)
     for it in range(1, 3):
         eng.iteration(it)
-    eng.set_debug(2)
+    eng.set_debug(hd.Debug.PHASE_TIMES)
     for it in range(3, 3 + args.iters):
         eng.iteration(it)
     eng.synchronize()

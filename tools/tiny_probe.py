@@ -27,7 +27,7 @@ for shape in [(n, int(os.environ.get("D", "3")), min(n, 2), 3)]:
         for n8, sm in [{"n8": (True, False), "sm": (False, True), "both": (True, True)}[mode]]:
             kw = dict(m=m, iterations=5, L=1, c_i=ds.truth, burnin=0, neal8=n8, split_merge=sm)
             st, ref = O.run_markov_chain(ds.codes, ds.attrisize, ds.gamma, ds.v, ds.w, seed=5, fast=1, **kw)
-            for dbg in [int(x) for x in os.environ.get("DBGS", "0,131072").split(",")]:
+            for dbg in [int(x) for x in os.environ.get("DBGS", f"0,{int(hd.Debug.NO_PREPASS_AHEAD)}").split(",")]:
                 e = hd.Engine(0)
                 e.set_data(ds.codes, ds.attrisize, ds.gamma, ds.v, ds.w)
                 e.set_seed(5)
