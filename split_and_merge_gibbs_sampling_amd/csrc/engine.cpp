@@ -33,12 +33,13 @@
 
 #include "../../include/hdpm.h"
 #include "host_topology.hpp"
+#include "host_util.hpp"
 #include "kernels.hpp"
 #include "mtjump.hpp"
 #include "phi_host.hpp"
 #include "pool_host.hpp"
 #include "rmath.hpp"
-#include "trace_tree.hpp"
+#include "summary_host.hpp"
 
 namespace hdpm {
 
@@ -75,34 +76,6 @@ hipError_t launch_hist(const HistArgs& a, hipStream_t s);
 size_t hist_partial_words(const HistArgs& a, int* nbx, int* kc, int* tpb);
 hipError_t launch_loglik(const LoglikArgs& a, hipStream_t s);
 hipError_t launch_mt_gen(const MtGenArgs& a, hipStream_t s);
-hipError_t launch_psm(const int32_t* trace, int M, int N, uint8_t* lab, uint32_t* cnt, hipStream_t s);
-hipError_t launch_vi_terms(const uint32_t* cnt, int N, int M, const int32_t* cls, int ncand, double* all, double* same,
-                           hipStream_t s);
-hipError_t launch_tr_pack(const int32_t* trace, int nm, int N, int Np, uint8_t* lab, hipStream_t s);
-hipError_t launch_tr_sizes(const uint8_t* lab, int Np, int M, uint32_t* sizes, hipStream_t s);
-hipError_t launch_tr_tables(const uint8_t* lab, const uint8_t* cls, int Np, int M, int ncand, int Ka, int Kz,
-                            uint32_t* tab, hipStream_t s);
-hipError_t launch_tr_gather(const uint8_t* lab, const uint8_t* cls, int N, int Np, int M, int ncand, int Ka, int Kz,
-                            const uint32_t* tab, const uint32_t* sizes, uint64_t* all, uint64_t* same,
-                            hipStream_t s);
-hipError_t launch_tr_reduce(const uint32_t* tab, int ncand, int M, int cells, uint64_t* q1, double* l1, uint64_t* q,
-                            double* l, hipStream_t s);
-hipError_t launch_tr_transpose(const uint32_t* tab, int M, int Ka, int Kz, uint32_t* tabT, hipStream_t s);
-hipError_t launch_tr_affinity(const uint8_t* lab, int Np, int M, int Ka, int Kz, const uint32_t* tabT, int i0, int npts,
-                              uint64_t* out, hipStream_t s);
-hipError_t launch_tr_cross(const uint32_t* tabT, int M, int Ka, int Kz, uint64_t* cross, hipStream_t s);
-hipError_t launch_tg_insert(const uint8_t* lab, int N, int Np, int M, int hash_bits, uint32_t tslots,
-                            uint32_t max_groups, uint32_t* rep, uint32_t* first, uint32_t* pslot, uint32_t* ctl,
-                            hipStream_t s);
-hipError_t launch_tg_finish(const uint8_t* lab, int N, int Np, int M, int U, int Mp, int Up, const uint32_t* pslot,
-                            const uint32_t* slot_gid, const uint32_t* first, uint32_t* group_of, uint32_t* weight,
-                            uint8_t* sig, uint8_t* sigT, hipStream_t s);
-hipError_t launch_tg_counts(const uint8_t* sig, int U, int M, int Mp, uint32_t* S, hipStream_t s);
-hipError_t launch_tg_tables(const uint8_t* sigT, const uint8_t* cut, const uint32_t* w, int U, int Up, int M, int ncut,
-                            int Ka, int Kz, uint32_t* tab, hipStream_t s);
-hipError_t launch_tg_gather(const uint8_t* sigT, const uint8_t* cut, int U, int Up, int M, int ncut, int Ka, int Kz,
-                            const uint32_t* tab, const uint32_t* sizes, uint64_t* all, uint64_t* same, hipStream_t s);
-hipError_t launch_tg_expand(const uint32_t* group_of, const int32_t* cut, int N, int32_t* cl, hipStream_t s);
 hipError_t launch_debug_draw(const double* logw, int E, double rU, int two_way, int ocml, int* out, hipStream_t s);
 hipError_t launch_debug_math(const double* x, int64_t n, int fn, int ocml, double* out, hipStream_t s);
 hipError_t launch_lmatrix(const uint8_t* codes_t, int n, int d, int nq, ParamTables cl, int K, double* L,
@@ -120,20 +93,9 @@ int phi_ilp();
 int sm_restricted_gibbs_device(struct Ctx* c, const int32_t* S, int32_t nS, int32_t i1, int32_t i2,
                                int32_t t);
 
-struct HipError {
-  hipError_t e;
-  const char* what;
-};
-#define HIPCHK(x)                                      \
-  do {                                                 \
-    hipError_t _e = (x);                               \
-    if (_e != hipSuccess) throw HipError{_e, #x};     \
-  } while (0)
-
 #ifndef HDPM_PHI_SPEC
 #define HDPM_PHI_SPEC 4   // update_phi phase B: first rbeta attempts speculated per batch
 #endif
-static std::atomic<int64_t> g_dev_allocs{0};   // device allocations made (diagnostics)
 
 // HDPM_SEGV_TRACE=1: a host fault prints the raw return addresses of the faulting stack and
 // the library's load address (for addr2line), then hands the signal to the handler that was
@@ -189,77 +151,6 @@ static const bool g_segv_trace = [] {
   sigemptyset(&sa.sa_mask);
   return sigaction(SIGSEGV, &sa, &g_segv_prev) == 0;
 }();
-
-template <class T>
-struct DevBuf {
-  T* p = nullptr;
-  size_t n = 0;
-  DevBuf() = default;
-  DevBuf(const DevBuf&) = delete;
-  DevBuf& operator=(const DevBuf&) = delete;
-  ~DevBuf() { release(); }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    n = 0;
-  }
-  // Grow to at least `count` elements; keep_old copies the previous contents.
-  void ensure(size_t count, bool keep_old = false, hipStream_t s = nullptr) {
-    if (count <= n && p) return;
-    T* np = nullptr;
-    g_dev_allocs.fetch_add(1, std::memory_order_relaxed);
-    HIPCHK(hipMalloc(&np, std::max<size_t>(count, 1) * sizeof(T)));
-    if (keep_old && p && n) {
-      HIPCHK(hipMemcpyAsync(np, p, n * sizeof(T), hipMemcpyDeviceToDevice, s));
-      HIPCHK(hipStreamSynchronize(s));
-    }
-    release();
-    p = np;
-    n = count;
-  }
-};
-
-template <class T>
-struct PinBuf {
-  T* p = nullptr;
-  size_t n = 0;
-  ~PinBuf() {
-    if (p) (void)hipHostFree(p);
-  }
-  // non-coherent (coarse-grained) by default: CPU-cached, so the host reads these buffers
-  // at cache speed; every device write to them is followed by a stream or event wait
-  // before use.  Buffers kernels read or write in place (no copy) are coherent.
-  void ensure(size_t count, unsigned flags = hipHostMallocNonCoherent) {
-    if (count <= n && p) return;
-    if (p) (void)hipHostFree(p);
-    p = nullptr;
-    HIPCHK(hipHostMalloc(&p, std::max<size_t>(count, 1) * sizeof(T), flags));
-    n = count;
-  }
-};
-
-static int host_threads() {
-  unsigned h = std::thread::hardware_concurrency();
-  if (h == 0) h = 4;
-  return (int)std::min<unsigned>(h, 16);
-}
-
-template <class F>
-static void parallel_for(int64_t n, F f) {
-  const int T = host_threads();
-  if (n < 4096 || T <= 1) {
-    f(0, n);
-    return;
-  }
-  std::vector<std::thread> th;
-  const int64_t chunk = (n + T - 1) / T;
-  for (int t = 0; t < T; ++t) {
-    int64_t a = t * chunk, b = std::min(n, a + chunk);
-    if (a >= b) break;
-    th.emplace_back([=] { f(a, b); });
-  }
-  for (auto& x : th) x.join();
-}
 
 // CPU list files of sysfs ("0-7,16-23").
 static std::vector<int> read_cpu_list(const std::string& path) {
@@ -770,42 +661,7 @@ struct Ctx {
   DevBuf<uint64_t> d_xbs;             // bit-sliced rows (tiled; prepass)
   DevBuf<double> d_logn;
   std::vector<double> h_logn;
-  // posterior analysis (hdpm_psm_*): label bytes, co-clustering counts, VI.lb sums
-  DevBuf<int32_t> d_psm_trace, d_psm_cls;
-  DevBuf<uint8_t> d_psm_lab;
-  DevBuf<uint32_t> d_psm_cnt;
-  DevBuf<double> d_psm_all, d_psm_same;
-  int psm_N = 0, psm_M = 0;
-  // matrix-free posterior summary (hdpm_trace_*): label bytes (M x Np), cluster sizes of the
-  // draws (M x 256), and per block of candidates their label bytes, contingency tables
-  // (nc x M x Ka x Kz), per-point sums and per-draw / per-candidate reductions
-  DevBuf<uint8_t> d_tr_lab, d_tr_cls;
-  DevBuf<uint32_t> d_tr_sizes, d_tr_tab;
-  DevBuf<uint64_t> d_tr_all, d_tr_same, d_tr_q1, d_tr_q;
-  DevBuf<double> d_tr_l1, d_tr_l;
-  int tr_N = 0, tr_M = 0, tr_Np = 0, tr_Kz = 0;
-  size_t tr_budget = 0;
-  uint64_t tr_P = 0;     // sum_m sum_b C2(n^m_b)
-  double tr_S = 0.0;     // sum_m sum_b n^m_b log2 n^m_b
-  // per draw (hdpm_trace_distances): P_m, S_m and the cluster count; the estimate's tables
-  // transposed, the staging of one block of points of aff, and cross (hdpm_trace_affinity)
-  std::vector<uint64_t> tr_Pm;
-  std::vector<double> tr_Sm;
-  std::vector<int32_t> tr_Km;
-  DevBuf<uint32_t> d_tr_tabT;
-  DevBuf<uint64_t> d_tr_aff, d_tr_cross;
-  // groups of equal label columns and their average-linkage tree (hdpm_trace_groups ..
-  // hdpm_trace_cut_labels): the open-addressing table, group_of per point, the groups'
-  // signatures both ways round, S (U x U) once it is first needed, the tree on the host
-  DevBuf<uint32_t> d_tg_rep, d_tg_slotfirst, d_tg_pslot, d_tg_ctl, d_tg_slotgid, d_tg_of, d_tg_first, d_tg_w, d_tg_S;
-  DevBuf<uint8_t> d_tg_sig, d_tg_sigT, d_tg_cut;
-  DevBuf<uint64_t> d_tg_all, d_tg_same;
-  DevBuf<int32_t> d_tg_cl, d_tg_cutw;
-  int tg_U = 0, tg_Mp = 0, tg_Up = 0;
-  bool tg_counts = false, tg_tree = false;
-  std::vector<uint32_t> tg_first, tg_w;
-  std::vector<int32_t> tg_merge;
-  std::vector<double> tg_height;
+  Summaries sum{stream, err};   // hdpm_psm_*, hdpm_trace_* (summary_host.hpp)
 
   Rng rng;
 
@@ -5219,78 +5075,6 @@ using hdpm::DevBuf;
     return HDPM_E_ARG;                                                         \
   }
 
-// ---- matrix-free posterior summary (trace_summary.hip): shared by the hdpm_trace_* calls
-constexpr size_t kTraceBudget = (size_t)256 << 20;   // default table bytes per block of candidates
-constexpr size_t kTraceMaxBlock = 64;                // candidates per block at most (their N x 8-byte sums)
-constexpr size_t kTraceStageWords = (size_t)16 << 20;   // labels uploaded per block of draws (64 MB)
-
-// the candidates' labels checked (0..254); *Ka = the largest cluster count among them
-static int trace_check(Ctx* ctx, const int32_t* cls, int ncand, int* Ka) {
-  if (ctx->tr_N == 0) { ctx->err = "trace: hdpm_trace_build has not been called"; return HDPM_E_ARG; }
-  if (!cls || ncand <= 0) { ctx->err = "trace: no candidate partitions"; return HDPM_E_ARG; }
-  int mx = 0;
-  for (int64_t q = 0; q < (int64_t)ncand * ctx->tr_N; ++q) {
-    if (cls[q] < 0 || cls[q] > 254) { ctx->err = "trace: candidate labels must be in 0..254"; return HDPM_E_ARG; }
-    mx = std::max(mx, cls[q]);
-  }
-  *Ka = mx + 1;
-  return HDPM_OK;
-}
-
-// The candidates in blocks of at most budget / (M x Ka x Kz x 4) (and kTraceMaxBlock): their
-// tables, then the per-point sums (terms; `all` with the first block if want_all) and the
-// per-candidate reductions (reduce); f(c0, nc) runs with the block's results on the device
-// and the stream drained.  A candidate's results do not depend on the block it falls in.
-template <class F>
-static void trace_blocks(Ctx* ctx, const int32_t* cls, int ncand, int Ka, bool terms, bool want_all, bool reduce, F f) {
-  const int N = ctx->tr_N, Np = ctx->tr_Np, M = ctx->tr_M, Kz = ctx->tr_Kz;
-  if (want_all && !terms && !reduce) {
-    // `all` alone needs the draws' sizes only: no tables, no candidate on the device; the
-    // gather runs its sizes row (candidate count 0) and f sees an empty first block
-    ctx->d_tr_all.ensure((size_t)N);
-    HIPCHK(hdpm::launch_tr_gather(ctx->d_tr_lab.p, nullptr, N, Np, M, 0, Ka, Kz, nullptr, ctx->d_tr_sizes.p,
-                                  ctx->d_tr_all.p, nullptr, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    f(0, 0);
-    return;
-  }
-  const size_t per = (size_t)M * Ka * Kz;
-  size_t cb = std::max<size_t>(1, ctx->tr_budget / (per * 4));
-  cb = std::min(std::min(cb, kTraceMaxBlock), (size_t)ncand);
-  ctx->d_tr_cls.ensure(cb * Np);
-  ctx->d_tr_tab.ensure(cb * per);
-  if (terms) ctx->d_tr_same.ensure(cb * N);
-  if (want_all) ctx->d_tr_all.ensure((size_t)N);
-  if (reduce) {
-    ctx->d_tr_q1.ensure(cb * M);
-    ctx->d_tr_l1.ensure(cb * M);
-    ctx->d_tr_q.ensure(cb);
-    ctx->d_tr_l.ensure(cb);
-  }
-  std::vector<uint8_t> bytes(cb * Np);
-  for (int c0 = 0; c0 < ncand; c0 += (int)cb) {
-    const int nc = std::min((int)cb, ncand - c0);
-    std::memset(bytes.data(), 0xFF, bytes.size());
-    for (int c = 0; c < nc; ++c) {
-      const int32_t* cl = cls + (size_t)(c0 + c) * N;
-      uint8_t* row = bytes.data() + (size_t)c * Np;
-      for (int i = 0; i < N; ++i) row[i] = (uint8_t)cl[i];
-    }
-    HIPCHK(hipMemcpyAsync(ctx->d_tr_cls.p, bytes.data(), (size_t)nc * Np, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(hipMemsetAsync(ctx->d_tr_tab.p, 0, (size_t)nc * per * 4, ctx->stream));
-    HIPCHK(hdpm::launch_tr_tables(ctx->d_tr_lab.p, ctx->d_tr_cls.p, Np, M, nc, Ka, Kz, ctx->d_tr_tab.p, ctx->stream));
-    if (terms)
-      HIPCHK(hdpm::launch_tr_gather(ctx->d_tr_lab.p, ctx->d_tr_cls.p, N, Np, M, nc, Ka, Kz, ctx->d_tr_tab.p,
-                                    ctx->d_tr_sizes.p, want_all && c0 == 0 ? ctx->d_tr_all.p : nullptr,
-                                    ctx->d_tr_same.p, ctx->stream));
-    if (reduce)
-      HIPCHK(hdpm::launch_tr_reduce(ctx->d_tr_tab.p, nc, M, Ka * Kz, ctx->d_tr_q1.p, ctx->d_tr_l1.p, ctx->d_tr_q.p,
-                                    ctx->d_tr_l.p, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    f(c0, nc);
-  }
-}
-
 extern "C" {
 
 int hdpm_device_count(void) {
@@ -5689,572 +5473,65 @@ int hdpm_set_option(hdpm_ctx* h, int32_t option, double value) {
       return HDPM_E_ARG;
   }
 }
+// ---- posterior summaries from saved labels (summary_host.cpp)
 int hdpm_psm_build(hdpm_ctx* h, const int32_t* c_trace, int32_t M, int32_t N) {
   CTX();
-  if (!c_trace || M <= 0 || N <= 0) return HDPM_E_ARG;
-  for (int64_t q = 0; q < (int64_t)M * N; ++q)
-    if (c_trace[q] < 0 || c_trace[q] > 254) { ctx->err = "psm: labels must be in 0..254"; return HDPM_E_ARG; }
-  GUARD({
-    const int Mp = (M + 15) & ~15;
-    ctx->d_psm_trace.ensure((size_t)M * N);
-    ctx->d_psm_lab.ensure((size_t)N * Mp);
-    ctx->d_psm_cnt.ensure((size_t)N * N);
-    HIPCHK(hipMemcpyAsync(ctx->d_psm_trace.p, c_trace, (size_t)M * N * 4, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(hdpm::launch_psm(ctx->d_psm_trace.p, M, N, ctx->d_psm_lab.p, ctx->d_psm_cnt.p, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    ctx->psm_N = N;
-    ctx->psm_M = M;
-    return HDPM_OK;
-  })
+  GUARD(return ctx->sum.psm_build(c_trace, M, N);)
 }
 int hdpm_psm_rows(hdpm_ctx* h, int32_t row0, int32_t nrows, double* out) {
   CTX();
-  const int N = ctx->psm_N;
-  if (!out || N == 0 || row0 < 0 || nrows < 0 || row0 + nrows > N) return HDPM_E_ARG;
-  GUARD({
-    std::vector<uint32_t> c((size_t)nrows * N);
-    HIPCHK(hipMemcpyAsync(c.data(), ctx->d_psm_cnt.p + (size_t)row0 * N, c.size() * 4, hipMemcpyDeviceToHost,
-                          ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    const double M = (double)ctx->psm_M;
-    for (size_t q = 0; q < c.size(); ++q) out[q] = (double)c[q] / M;
-    return HDPM_OK;
-  })
+  GUARD(return ctx->sum.psm_rows(row0, nrows, out);)
 }
 int hdpm_psm_vi_lb(hdpm_ctx* h, const int32_t* cls, int32_t ncand, double* out) {
   CTX();
-  const int N = ctx->psm_N;
-  if (!cls || !out || N == 0 || ncand <= 0) return HDPM_E_ARG;
-  GUARD({
-    ctx->d_psm_cls.ensure((size_t)ncand * N);
-    ctx->d_psm_all.ensure((size_t)N);
-    ctx->d_psm_same.ensure((size_t)ncand * N);
-    HIPCHK(hipMemcpyAsync(ctx->d_psm_cls.p, cls, (size_t)ncand * N * 4, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(hdpm::launch_vi_terms(ctx->d_psm_cnt.p, N, ctx->psm_M, ctx->d_psm_cls.p, ncand, ctx->d_psm_all.p,
-                                 ctx->d_psm_same.p, ctx->stream));
-    std::vector<double> all((size_t)N);
-    std::vector<double> same((size_t)ncand * N);
-    HIPCHK(hipMemcpyAsync(all.data(), ctx->d_psm_all.p, all.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipMemcpyAsync(same.data(), ctx->d_psm_same.p, same.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    // mcclust.ext VI.lb: f = sum_i (log2 n_{c_i} + log2 sum_j psm_ij - 2 log2 sum_{j in c_i} psm_ij) / n
-    std::vector<int> sz;
-    for (int c = 0; c < ncand; ++c) {
-      const int32_t* cl = cls + (size_t)c * N;
-      int mx = 0;
-      for (int i = 0; i < N; ++i) mx = std::max(mx, cl[i]);
-      sz.assign((size_t)mx + 1, 0);
-      for (int i = 0; i < N; ++i) {
-        if (cl[i] < 0) { ctx->err = "psm: negative cluster label"; return HDPM_E_ARG; }
-        sz[cl[i]]++;
-      }
-      double f = 0.0;
-      for (int i = 0; i < N; ++i)
-        f = f + (std::log2((double)sz[cl[i]]) + std::log2(all[i]) - 2 * std::log2(same[(size_t)c * N + i])) / N;
-      out[c] = f;
-    }
-    return HDPM_OK;
-  })
+  GUARD(return ctx->sum.psm_vi_lb(cls, ncand, out);)
 }
 int hdpm_trace_build(hdpm_ctx* h, const int32_t* c_trace, int32_t M, int32_t N, int64_t table_budget_bytes) {
   CTX();
-  if (!c_trace || M <= 0 || N <= 0 || table_budget_bytes < 0) { ctx->err = "trace: bad arguments"; return HDPM_E_ARG; }
-  int mx = 0;
-  for (int64_t q = 0; q < (int64_t)M * N; ++q) {
-    if (c_trace[q] < 0 || c_trace[q] > 254) { ctx->err = "trace: labels must be in 0..254"; return HDPM_E_ARG; }
-    mx = std::max(mx, c_trace[q]);
-  }
-  GUARD({
-    ctx->tr_N = 0;   // no trace until this one is complete
-    ctx->tg_U = 0;   // and no groups or tree of the previous one
-    ctx->tg_counts = ctx->tg_tree = false;
-    const int Np = (int)(((int64_t)N + 15) & ~(int64_t)15);
-    ctx->d_tr_lab.ensure((size_t)M * Np);
-    ctx->d_tr_sizes.ensure((size_t)M * 256);
-    ctx->d_tr_q1.ensure((size_t)M);
-    ctx->d_tr_l1.ensure((size_t)M);
-    ctx->d_tr_q.ensure(1);
-    ctx->d_tr_l.ensure(1);
-    {
-      // the int32 labels go up in blocks of draws through one staging buffer, freed at the end
-      const int mb = (int)std::min<size_t>((size_t)M, std::max<size_t>(1, kTraceStageWords / (size_t)N));
-      DevBuf<int32_t> stage;
-      stage.ensure((size_t)mb * N);
-      for (int m0 = 0; m0 < M; m0 += mb) {
-        const int nm = std::min(mb, M - m0);
-        HIPCHK(hipMemcpyAsync(stage.p, c_trace + (size_t)m0 * N, (size_t)nm * N * 4, hipMemcpyHostToDevice,
-                              ctx->stream));
-        HIPCHK(hdpm::launch_tr_pack(stage.p, nm, N, Np, ctx->d_tr_lab.p + (size_t)m0 * Np, ctx->stream));
-      }
-      HIPCHK(hipStreamSynchronize(ctx->stream));
-    }
-    HIPCHK(hipMemsetAsync(ctx->d_tr_sizes.p, 0, (size_t)M * 256 * 4, ctx->stream));
-    HIPCHK(hdpm::launch_tr_sizes(ctx->d_tr_lab.p, Np, M, ctx->d_tr_sizes.p, ctx->stream));
-    HIPCHK(hdpm::launch_tr_reduce(ctx->d_tr_sizes.p, 1, M, 256, ctx->d_tr_q1.p, ctx->d_tr_l1.p, ctx->d_tr_q.p,
-                                  ctx->d_tr_l.p, ctx->stream));
-    HIPCHK(hipMemcpyAsync(&ctx->tr_P, ctx->d_tr_q.p, 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipMemcpyAsync(&ctx->tr_S, ctx->d_tr_l.p, 8, hipMemcpyDeviceToHost, ctx->stream));
-    // the per-draw P_m and S_m stay on the host (later calls reuse d_tr_q1 / d_tr_l1), with
-    // the draws' cluster counts from the size rows
-    ctx->tr_Pm.resize((size_t)M);
-    ctx->tr_Sm.resize((size_t)M);
-    ctx->tr_Km.assign((size_t)M, 0);
-    std::vector<uint32_t> sizes((size_t)M * 256);
-    HIPCHK(hipMemcpyAsync(ctx->tr_Pm.data(), ctx->d_tr_q1.p, (size_t)M * 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipMemcpyAsync(ctx->tr_Sm.data(), ctx->d_tr_l1.p, (size_t)M * 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipMemcpyAsync(sizes.data(), ctx->d_tr_sizes.p, sizes.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    for (int m = 0; m < M; ++m)
-      for (int b = 0; b < 256; ++b) ctx->tr_Km[m] += sizes[(size_t)m * 256 + b] != 0u;
-    ctx->tr_M = M;
-    ctx->tr_Np = Np;
-    ctx->tr_Kz = mx + 1;
-    ctx->tr_budget = table_budget_bytes > 0 ? (size_t)table_budget_bytes : kTraceBudget;
-    ctx->tr_N = N;
-    return HDPM_OK;
-  })
+  GUARD(return ctx->sum.trace_build(c_trace, M, N, table_budget_bytes);)
 }
 int hdpm_trace_terms(hdpm_ctx* h, const int32_t* cls, int32_t ncand, uint64_t* all, uint64_t* same) {
   CTX();
-  int Ka = 0;
-  if (int st = trace_check(ctx, cls, ncand, &Ka)) return st;
-  if (!all && !same) return HDPM_OK;
-  GUARD({
-    const size_t N = (size_t)ctx->tr_N;
-    trace_blocks(ctx, cls, ncand, Ka, same != nullptr, all != nullptr, false, [&](int c0, int nc) {
-      if (all && c0 == 0) HIPCHK(hipMemcpyAsync(all, ctx->d_tr_all.p, N * 8, hipMemcpyDeviceToHost, ctx->stream));
-      if (same)
-        HIPCHK(hipMemcpyAsync(same + (size_t)c0 * N, ctx->d_tr_same.p, (size_t)nc * N * 8, hipMemcpyDeviceToHost,
-                              ctx->stream));
-      HIPCHK(hipStreamSynchronize(ctx->stream));
-    });
-    return HDPM_OK;
-  })
+  GUARD(return ctx->sum.trace_terms(cls, ncand, all, same);)
 }
 int hdpm_trace_losses(hdpm_ctx* h, const int32_t* cls, int32_t ncand, double* vi_lb, double* vi, uint64_t* binder_Q,
                       uint64_t* binder_P) {
   CTX();
-  int Ka = 0;
-  if (int st = trace_check(ctx, cls, ncand, &Ka)) return st;
-  GUARD({
-    const int N = ctx->tr_N;
-    const double dM = (double)ctx->tr_M;
-    if (binder_P) *binder_P = ctx->tr_P;
-    if (!vi_lb && !vi && !binder_Q) return HDPM_OK;
-    std::vector<uint64_t> all, same, q;
-    std::vector<double> lall, term, l, lsz((size_t)Ka);
-    std::vector<int> sz((size_t)Ka);
-    trace_blocks(ctx, cls, ncand, Ka, vi_lb != nullptr, vi_lb != nullptr, vi || binder_Q, [&](int c0, int nc) {
-      if (vi_lb) {
-        if (c0 == 0) {
-          all.resize((size_t)N);
-          HIPCHK(hipMemcpyAsync(all.data(), ctx->d_tr_all.p, (size_t)N * 8, hipMemcpyDeviceToHost, ctx->stream));
-        }
-        same.resize((size_t)nc * N);
-        HIPCHK(hipMemcpyAsync(same.data(), ctx->d_tr_same.p, same.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
-      }
-      if (vi || binder_Q) {
-        q.resize((size_t)nc);
-        l.resize((size_t)nc);
-        HIPCHK(hipMemcpyAsync(q.data(), ctx->d_tr_q.p, (size_t)nc * 8, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(hipMemcpyAsync(l.data(), ctx->d_tr_l.p, (size_t)nc * 8, hipMemcpyDeviceToHost, ctx->stream));
-      }
-      HIPCHK(hipStreamSynchronize(ctx->stream));
-      if (vi_lb && c0 == 0) {
-        // log2 sum_j psm_ij is the same for every candidate
-        lall.resize((size_t)N);
-        term.resize((size_t)N);
-        hdpm::parallel_for(N, [&](int64_t i0, int64_t i1) {
-          for (int64_t i = i0; i < i1; ++i) lall[i] = std::log2((double)all[i] / dM);
-        });
-      }
-      for (int c = 0; c < nc; ++c) {
-        const int32_t* cl = cls + (size_t)(c0 + c) * N;
-        std::fill(sz.begin(), sz.end(), 0);
-        for (int i = 0; i < N; ++i) sz[cl[i]]++;
-        for (int a = 0; a < Ka; ++a) lsz[a] = sz[a] > 0 ? std::log2((double)sz[a]) : 0.0;
-        if (vi_lb) {
-          // the expression of hdpm_psm_vi_lb, with psm sums = integer sums / M
-          // (the terms on the host's threads, their sum in index order as there)
-          const uint64_t* sm = same.data() + (size_t)c * N;
-          hdpm::parallel_for(N, [&](int64_t i0, int64_t i1) {
-            for (int64_t i = i0; i < i1; ++i)
-              term[i] = (lsz[cl[i]] + lall[i] - 2 * std::log2((double)sm[i] / dM)) / N;
-          });
-          double f = 0.0;
-          for (int i = 0; i < N; ++i) f = f + term[i];
-          vi_lb[c0 + c] = f;
-        }
-        if (vi) {
-          // mcclust.ext VI(cls, cls.draw): (sum_a n_a log2 n_a + (S - 2 sum_m sum_ab T log2 T) / M) / N
-          double hc = 0.0;
-          for (int a = 0; a < Ka; ++a) hc = hc + (double)sz[a] * lsz[a];
-          vi[c0 + c] = (hc + (ctx->tr_S - 2 * l[c]) / dM) / N;
-        }
-        if (binder_Q) binder_Q[c0 + c] = q[c];
-      }
-    });
-    return HDPM_OK;
-  })
+  GUARD(return ctx->sum.trace_losses(cls, ncand, vi_lb, vi, binder_Q, binder_P);)
 }
 int hdpm_trace_tables(hdpm_ctx* h, const int32_t* cls, int32_t ncand, int32_t m0, int32_t nm, uint32_t* out) {
   CTX();
-  int Ka = 0;
-  if (int st = trace_check(ctx, cls, ncand, &Ka)) return st;
-  if (!out || m0 < 0 || nm <= 0 || (int64_t)m0 + nm > ctx->tr_M) {
-    ctx->err = "trace: draws m0 .. m0 + nm - 1 must lie in 0 .. M - 1";
-    return HDPM_E_ARG;
-  }
-  GUARD({
-    const int M = ctx->tr_M, Kz = ctx->tr_Kz;
-    const size_t cells = (size_t)Ka * Kz;
-    std::memset(out, 0, (size_t)ncand * nm * 65536 * 4);
-    std::vector<uint32_t> t((size_t)nm * cells);
-    trace_blocks(ctx, cls, ncand, Ka, false, false, false, [&](int c0, int nc) {
-      for (int c = 0; c < nc; ++c) {
-        HIPCHK(hipMemcpyAsync(t.data(), ctx->d_tr_tab.p + ((size_t)c * M + m0) * cells, t.size() * 4,
-                              hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(hipStreamSynchronize(ctx->stream));
-        for (int m = 0; m < nm; ++m)
-          for (int a = 0; a < Ka; ++a)
-            std::memcpy(out + (((size_t)(c0 + c) * nm + m) * 256 + a) * 256, t.data() + ((size_t)m * Ka + a) * Kz,
-                        (size_t)Kz * 4);
-      }
-    });
-    return HDPM_OK;
-  })
+  GUARD(return ctx->sum.trace_tables(cls, ncand, m0, nm, out);)
 }
-// ---- how far the estimate can be trusted (trace_uncertainty.hip)
 int hdpm_trace_distances(hdpm_ctx* h, const int32_t* cls, int32_t ncand, double* vi, uint64_t* binder,
                          int32_t* draw_k) {
   CTX();
-  int Ka = 0;
-  if (int st = trace_check(ctx, cls, ncand, &Ka)) return st;
-  GUARD({
-    const int N = ctx->tr_N, M = ctx->tr_M;
-    if (draw_k) std::memcpy(draw_k, ctx->tr_Km.data(), (size_t)M * 4);
-    if (!vi && !binder) return HDPM_OK;
-    std::vector<uint64_t> q1;
-    std::vector<double> l1, lsz((size_t)Ka);
-    std::vector<int> sz((size_t)Ka);
-    // the per-(candidate, draw) sums of k_tr_reduce, as they stand before k_tr_reduce_draws
-    trace_blocks(ctx, cls, ncand, Ka, false, false, true, [&](int c0, int nc) {
-      q1.resize((size_t)nc * M);
-      l1.resize((size_t)nc * M);
-      HIPCHK(hipMemcpyAsync(q1.data(), ctx->d_tr_q1.p, q1.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
-      HIPCHK(hipMemcpyAsync(l1.data(), ctx->d_tr_l1.p, l1.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
-      HIPCHK(hipStreamSynchronize(ctx->stream));
-      for (int c = 0; c < nc; ++c) {
-        const int32_t* cl = cls + (size_t)(c0 + c) * N;
-        std::fill(sz.begin(), sz.end(), 0);
-        for (int i = 0; i < N; ++i) sz[cl[i]]++;
-        for (int a = 0; a < Ka; ++a) lsz[a] = sz[a] > 0 ? std::log2((double)sz[a]) : 0.0;
-        // hc as in hdpm_trace_losses; A_c = sum_a C2(n_a)
-        double hc = 0.0;
-        uint64_t A = 0;
-        for (int a = 0; a < Ka; ++a) {
-          hc = hc + (double)sz[a] * lsz[a];
-          A += (uint64_t)sz[a] * (uint64_t)(sz[a] > 0 ? sz[a] - 1 : 0) / 2;
-        }
-        for (int m = 0; m < M; ++m) {
-          const size_t o = (size_t)(c0 + c) * M + m, k = (size_t)c * M + m;
-          if (vi) {
-            const double d = (hc + ctx->tr_Sm[m] - 2 * l1[k]) / N;
-            vi[o] = d < 0.0 ? 0.0 : d;      // rounding can undershoot 0 when c is the draw
-          }
-          if (binder) binder[o] = A + ctx->tr_Pm[m] - 2 * q1[k];
-        }
-      }
-    });
-    return HDPM_OK;
-  })
+  GUARD(return ctx->sum.trace_distances(cls, ncand, vi, binder, draw_k);)
 }
 int hdpm_trace_affinity(hdpm_ctx* h, const int32_t* cl, int32_t Ka, uint64_t* aff, uint64_t* cross) {
   CTX();
-  int used = 0;   // the largest label + 1
-  if (int st = trace_check(ctx, cl, 1, &used)) return st;
-  if (Ka < 1 || Ka > 255) { ctx->err = "trace: Ka must be in 1..255"; return HDPM_E_ARG; }
-  if (used > Ka) { ctx->err = "trace: the partition's labels must be in 0..Ka-1"; return HDPM_E_ARG; }
-  const int N = ctx->tr_N, Np = ctx->tr_Np, M = ctx->tr_M, Kz = ctx->tr_Kz;
-  if (cross && ((unsigned __int128)N * (unsigned __int128)N * (unsigned __int128)M >> 63)) {
-    ctx->err = "trace: N^2 M does not fit 63 bits: the sums of cross would overflow";
-    return HDPM_E_ARG;
-  }
-  if (!aff && !cross) return HDPM_OK;
-  GUARD({
-    // one candidate always fits a block of trace_blocks: its tables, then their transpose
-    trace_blocks(ctx, cl, 1, Ka, false, false, false, [&](int, int) {
-      const size_t per = (size_t)M * Ka * Kz;
-      ctx->d_tr_tabT.ensure(per);
-      HIPCHK(hdpm::launch_tr_transpose(ctx->d_tr_tab.p, M, Ka, Kz, ctx->d_tr_tabT.p, ctx->stream));
-      if (cross) {
-        ctx->d_tr_cross.ensure((size_t)Ka * Ka);
-        HIPCHK(hipMemsetAsync(ctx->d_tr_cross.p, 0, (size_t)Ka * Ka * 8, ctx->stream));
-        HIPCHK(hdpm::launch_tr_cross(ctx->d_tr_tabT.p, M, Ka, Kz, ctx->d_tr_cross.p, ctx->stream));
-        HIPCHK(hipMemcpyAsync(cross, ctx->d_tr_cross.p, (size_t)Ka * Ka * 8, hipMemcpyDeviceToHost, ctx->stream));
-      }
-      if (aff) {
-        // blocks of points: the staging (pb x Ka x 8 bytes) within the table budget, in whole
-        // groups of 16 points and at least one; each block goes to the caller as it completes
-        size_t pb = (ctx->tr_budget / ((size_t)Ka * 8)) & ~(size_t)15;
-        pb = std::min(std::max<size_t>(pb, 16), (size_t)Np);
-        ctx->d_tr_aff.ensure(pb * Ka);
-        for (int64_t i0 = 0; i0 < N; i0 += (int64_t)pb) {
-          const int np = (int)std::min<int64_t>((int64_t)pb, N - i0);
-          HIPCHK(hdpm::launch_tr_affinity(ctx->d_tr_lab.p, Np, M, Ka, Kz, ctx->d_tr_tabT.p, (int)i0, np,
-                                          ctx->d_tr_aff.p, ctx->stream));
-          HIPCHK(hipMemcpyAsync(aff + (size_t)i0 * Ka, ctx->d_tr_aff.p, (size_t)np * Ka * 8, hipMemcpyDeviceToHost,
-                                ctx->stream));
-          HIPCHK(hipStreamSynchronize(ctx->stream));
-        }
-      }
-      HIPCHK(hipStreamSynchronize(ctx->stream));
-    });
-    return HDPM_OK;
-  })
-}
-// ---- average-linkage search on the groups of equal label columns (trace_summary.hip k_tg_*,
-// trace_tree.hpp)
-static int tg_need(Ctx* ctx, bool tree) {
-  if (ctx->tr_N == 0) { ctx->err = "trace: hdpm_trace_build has not been called"; return HDPM_E_ARG; }
-  if (ctx->tg_U == 0) { ctx->err = "trace: hdpm_trace_groups has not been called"; return HDPM_E_ARG; }
-  if (tree && !ctx->tg_tree) { ctx->err = "trace: hdpm_trace_avg_tree has not been called"; return HDPM_E_ARG; }
-  return HDPM_OK;
-}
-static void tg_counts(Ctx* ctx) {
-  if (ctx->tg_counts) return;
-  const size_t U = (size_t)ctx->tg_U;
-  ctx->d_tg_S.ensure(U * U);
-  HIPCHK(hdpm::launch_tg_counts(ctx->d_tg_sig.p, ctx->tg_U, ctx->tr_M, ctx->tg_Mp, ctx->d_tg_S.p, ctx->stream));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  ctx->tg_counts = true;
+  GUARD(return ctx->sum.trace_affinity(cl, Ka, aff, cross);)
 }
 int hdpm_trace_groups(hdpm_ctx* h, int32_t max_groups, int32_t hash_bits, int32_t* U_out) {
   CTX();
-  if (ctx->tr_N == 0) { ctx->err = "trace: hdpm_trace_build has not been called"; return HDPM_E_ARG; }
-  if (max_groups == 0) max_groups = HDPM_TRACE_GROUPS_DEFAULT;
-  if (max_groups < 0 || max_groups > HDPM_TRACE_GROUPS_MAX || hash_bits < 0 || hash_bits > 32) {
-    ctx->err = "trace: max_groups must be in 1.." + std::to_string(HDPM_TRACE_GROUPS_MAX) + " and hash_bits in 0..32";
-    return HDPM_E_ARG;
-  }
-  const int N = ctx->tr_N, Np = ctx->tr_Np, M = ctx->tr_M;
-  if ((unsigned __int128)N * (unsigned __int128)N * (unsigned __int128)M >> 63) {
-    ctx->err = "trace: N^2 M does not fit 63 bits: the tree's integer sums would overflow";
-    return HDPM_E_ARG;
-  }
-  GUARD({
-    ctx->tg_U = 0;
-    ctx->tg_counts = ctx->tg_tree = false;
-    uint32_t T = 1024;
-    while (T < 4u * (uint32_t)max_groups) T <<= 1;
-    ctx->d_tg_rep.ensure(T);
-    ctx->d_tg_slotfirst.ensure(T);
-    ctx->d_tg_slotgid.ensure(T);
-    ctx->d_tg_pslot.ensure((size_t)N);
-    ctx->d_tg_ctl.ensure(2);
-    HIPCHK(hipMemsetAsync(ctx->d_tg_rep.p, 0xFF, (size_t)T * 4, ctx->stream));
-    HIPCHK(hipMemsetAsync(ctx->d_tg_slotfirst.p, 0xFF, (size_t)T * 4, ctx->stream));
-    HIPCHK(hipMemsetAsync(ctx->d_tg_ctl.p, 0, 8, ctx->stream));
-    HIPCHK(hdpm::launch_tg_insert(ctx->d_tr_lab.p, N, Np, M, hash_bits, T, (uint32_t)max_groups, ctx->d_tg_rep.p,
-                                  ctx->d_tg_slotfirst.p, ctx->d_tg_pslot.p, ctx->d_tg_ctl.p, ctx->stream));
-    uint32_t ctl[2] = {0u, 0u};
-    std::vector<uint32_t> sf((size_t)T);
-    HIPCHK(hipMemcpyAsync(ctl, ctx->d_tg_ctl.p, 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipMemcpyAsync(sf.data(), ctx->d_tg_slotfirst.p, (size_t)T * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    if (ctl[1]) {
-      ctx->err = "trace: more than max_groups = " + std::to_string(max_groups) +
-                 " distinct label columns: the trace is too unsettled for the average-linkage search";
-      return HDPM_E_ARG;
-    }
-    // the groups numbered by ascending smallest member: whichever slot a column landed in
-    std::vector<std::pair<uint32_t, uint32_t>> order;
-    for (uint32_t s = 0; s < T; ++s)
-      if (sf[s] != 0xFFFFFFFFu) order.emplace_back(sf[s], s);
-    std::sort(order.begin(), order.end());
-    const int U = (int)order.size();
-    if (U == 0 || (uint32_t)U != ctl[0]) { ctx->err = "trace: the group table is inconsistent"; return HDPM_E_DEVICE; }
-    std::vector<uint32_t> gid((size_t)T, 0u);
-    ctx->tg_first.resize((size_t)U);
-    for (int u = 0; u < U; ++u) {
-      ctx->tg_first[u] = order[u].first;
-      gid[order[u].second] = (uint32_t)u;
-    }
-    const int Mp = (M + 63) & ~63, Up = (U + 15) & ~15;
-    ctx->d_tg_of.ensure((size_t)N);
-    ctx->d_tg_first.ensure((size_t)U);
-    ctx->d_tg_w.ensure((size_t)U);
-    ctx->d_tg_sig.ensure((size_t)U * Mp);
-    ctx->d_tg_sigT.ensure((size_t)M * Up);
-    HIPCHK(hipMemcpyAsync(ctx->d_tg_slotgid.p, gid.data(), (size_t)T * 4, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(hipMemcpyAsync(ctx->d_tg_first.p, ctx->tg_first.data(), (size_t)U * 4, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(hipMemsetAsync(ctx->d_tg_w.p, 0, (size_t)U * 4, ctx->stream));
-    HIPCHK(hdpm::launch_tg_finish(ctx->d_tr_lab.p, N, Np, M, U, Mp, Up, ctx->d_tg_pslot.p, ctx->d_tg_slotgid.p,
-                                  ctx->d_tg_first.p, ctx->d_tg_of.p, ctx->d_tg_w.p, ctx->d_tg_sig.p, ctx->d_tg_sigT.p,
-                                  ctx->stream));
-    ctx->tg_w.resize((size_t)U);
-    HIPCHK(hipMemcpyAsync(ctx->tg_w.data(), ctx->d_tg_w.p, (size_t)U * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    ctx->tg_Mp = Mp;
-    ctx->tg_Up = Up;
-    ctx->tg_U = U;
-    if (U_out) *U_out = U;
-    return HDPM_OK;
-  })
+  GUARD(return ctx->sum.trace_groups(max_groups, hash_bits, U_out);)
 }
 int hdpm_trace_group_info(hdpm_ctx* h, int32_t* first, int32_t* weight, int32_t* group_of, uint32_t* counts) {
   CTX();
-  if (int st = tg_need(ctx, false)) return st;
-  GUARD({
-    const size_t U = (size_t)ctx->tg_U;
-    if (first) std::memcpy(first, ctx->tg_first.data(), U * 4);
-    if (weight) std::memcpy(weight, ctx->tg_w.data(), U * 4);
-    if (group_of)
-      HIPCHK(hipMemcpyAsync(group_of, ctx->d_tg_of.p, (size_t)ctx->tr_N * 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (counts) {
-      tg_counts(ctx);
-      HIPCHK(hipMemcpyAsync(counts, ctx->d_tg_S.p, U * U * 4, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    return HDPM_OK;
-  })
+  GUARD(return ctx->sum.trace_group_info(first, weight, group_of, counts);)
 }
 int hdpm_trace_avg_tree(hdpm_ctx* h, int32_t* merge, double* height) {
   CTX();
-  if (int st = tg_need(ctx, false)) return st;
-  GUARD({
-    const size_t U = (size_t)ctx->tg_U;
-    if (!ctx->tg_tree) {
-      tg_counts(ctx);
-      std::vector<uint32_t> S(U * U);
-      HIPCHK(hipMemcpyAsync(S.data(), ctx->d_tg_S.p, U * U * 4, hipMemcpyDeviceToHost, ctx->stream));
-      HIPCHK(hipStreamSynchronize(ctx->stream));
-      std::vector<uint64_t> w(ctx->tg_w.begin(), ctx->tg_w.end()), first(ctx->tg_first.begin(), ctx->tg_first.end());
-      ctx->tg_merge.assign((U - 1) * 2, 0);
-      ctx->tg_height.assign(U - 1, 0.0);
-      hdpm::tt_avg_linkage((int)U, w.data(), first.data(), S.data(), (uint64_t)ctx->tr_M, ctx->tg_merge.data(),
-                           ctx->tg_height.data());
-      ctx->tg_tree = true;
-    }
-    if (merge && U > 1) std::memcpy(merge, ctx->tg_merge.data(), (U - 1) * 2 * 4);
-    if (height && U > 1) std::memcpy(height, ctx->tg_height.data(), (U - 1) * 8);
-    return HDPM_OK;
-  })
+  GUARD(return ctx->sum.trace_avg_tree(merge, height);)
 }
 int hdpm_trace_cut_losses(hdpm_ctx* h, int32_t k0, int32_t nk, double* vi_lb, double* vi, uint64_t* binder_A,
                           uint64_t* binder_Q) {
   CTX();
-  if (int st = tg_need(ctx, true)) return st;
-  if (k0 < 1 || nk < 1 || (int64_t)k0 + nk - 1 > std::min(ctx->tg_U, 255)) {
-    ctx->err = "trace: cuts k0 .. k0 + nk - 1 must lie in 1 .. min(U, 255)";
-    return HDPM_E_ARG;
-  }
-  GUARD({
-    const int N = ctx->tr_N, M = ctx->tr_M, Kz = ctx->tr_Kz, U = ctx->tg_U, Up = ctx->tg_Up, Ka = k0 + nk - 1;
-    const double dM = (double)M;
-    if (!vi_lb && !vi && !binder_A && !binder_Q) return HDPM_OK;
-    const bool reduce = vi || binder_Q;
-    const size_t per = (size_t)M * Ka * Kz;
-    size_t cb = std::max<size_t>(1, ctx->tr_budget / (per * 4));
-    cb = std::min(std::min(cb, kTraceMaxBlock), (size_t)nk);
-    ctx->d_tg_cut.ensure(cb * Up);
-    ctx->d_tr_tab.ensure(cb * per);
-    if (vi_lb) {
-      ctx->d_tg_all.ensure((size_t)U);
-      ctx->d_tg_same.ensure(cb * U);
-    }
-    if (reduce) {
-      ctx->d_tr_q1.ensure(cb * M);
-      ctx->d_tr_l1.ensure(cb * M);
-      ctx->d_tr_q.ensure(cb);
-      ctx->d_tr_l.ensure(cb);
-    }
-    std::vector<uint8_t> bytes(cb * Up);
-    std::vector<int32_t> cut((size_t)U);
-    std::vector<uint64_t> all, same, q, sz((size_t)Ka);
-    std::vector<double> lall, l, lsz((size_t)Ka);
-    for (int c0 = 0; c0 < nk; c0 += (int)cb) {
-      const int nc = std::min((int)cb, nk - c0);
-      std::memset(bytes.data(), 0xFF, bytes.size());
-      for (int c = 0; c < nc; ++c) {
-        hdpm::tt_cut(U, ctx->tg_merge.data(), k0 + c0 + c, cut.data());
-        for (int u = 0; u < U; ++u) bytes[(size_t)c * Up + u] = (uint8_t)cut[u];
-      }
-      HIPCHK(hipMemcpyAsync(ctx->d_tg_cut.p, bytes.data(), (size_t)nc * Up, hipMemcpyHostToDevice, ctx->stream));
-      HIPCHK(hipMemsetAsync(ctx->d_tr_tab.p, 0, (size_t)nc * per * 4, ctx->stream));
-      HIPCHK(hdpm::launch_tg_tables(ctx->d_tg_sigT.p, ctx->d_tg_cut.p, ctx->d_tg_w.p, U, Up, M, nc, Ka, Kz,
-                                    ctx->d_tr_tab.p, ctx->stream));
-      if (vi_lb) {
-        HIPCHK(hdpm::launch_tg_gather(ctx->d_tg_sigT.p, ctx->d_tg_cut.p, U, Up, M, nc, Ka, Kz, ctx->d_tr_tab.p,
-                                      ctx->d_tr_sizes.p, c0 == 0 ? ctx->d_tg_all.p : nullptr, ctx->d_tg_same.p,
-                                      ctx->stream));
-        if (c0 == 0) {
-          all.resize((size_t)U);
-          HIPCHK(hipMemcpyAsync(all.data(), ctx->d_tg_all.p, (size_t)U * 8, hipMemcpyDeviceToHost, ctx->stream));
-        }
-        same.resize((size_t)nc * U);
-        HIPCHK(hipMemcpyAsync(same.data(), ctx->d_tg_same.p, same.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
-      }
-      if (reduce) {
-        HIPCHK(hdpm::launch_tr_reduce(ctx->d_tr_tab.p, nc, M, Ka * Kz, ctx->d_tr_q1.p, ctx->d_tr_l1.p, ctx->d_tr_q.p,
-                                      ctx->d_tr_l.p, ctx->stream));
-        q.resize((size_t)nc);
-        l.resize((size_t)nc);
-        HIPCHK(hipMemcpyAsync(q.data(), ctx->d_tr_q.p, (size_t)nc * 8, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(hipMemcpyAsync(l.data(), ctx->d_tr_l.p, (size_t)nc * 8, hipMemcpyDeviceToHost, ctx->stream));
-      }
-      HIPCHK(hipStreamSynchronize(ctx->stream));
-      if (vi_lb && c0 == 0) {
-        lall.resize((size_t)U);
-        for (int u = 0; u < U; ++u) lall[u] = std::log2((double)all[u] / dM);
-      }
-      for (int c = 0; c < nc; ++c) {
-        const uint8_t* cl = bytes.data() + (size_t)c * Up;
-        std::fill(sz.begin(), sz.end(), 0);
-        for (int u = 0; u < U; ++u) sz[cl[u]] += ctx->tg_w[u];
-        for (int a = 0; a < Ka; ++a) lsz[a] = sz[a] > 0 ? std::log2((double)sz[a]) : 0.0;
-        if (vi_lb) {
-          // the per-point term of hdpm_trace_losses, once per group and weighted by its size
-          const uint64_t* sm = same.data() + (size_t)c * U;
-          long double f = 0.0L;
-          for (int u = 0; u < U; ++u) {
-            const double term = (lsz[cl[u]] + lall[u] - 2 * std::log2((double)sm[u] / dM)) / N;
-            f += (long double)ctx->tg_w[u] * (long double)term;
-          }
-          vi_lb[c0 + c] = (double)f;
-        }
-        if (vi) {
-          double hc = 0.0;
-          for (int a = 0; a < Ka; ++a) hc = hc + (double)sz[a] * lsz[a];
-          vi[c0 + c] = (hc + (ctx->tr_S - 2 * l[c]) / dM) / N;
-        }
-        if (binder_A) {
-          uint64_t A = 0;
-          for (int a = 0; a < Ka; ++a) A += sz[a] * (sz[a] - (sz[a] > 0 ? 1 : 0)) / 2;
-          binder_A[c0 + c] = A;
-        }
-        if (binder_Q) binder_Q[c0 + c] = q[c];
-      }
-    }
-    return HDPM_OK;
-  })
+  GUARD(return ctx->sum.trace_cut_losses(k0, nk, vi_lb, vi, binder_A, binder_Q);)
 }
 int hdpm_trace_cut_labels(hdpm_ctx* h, int32_t k, int32_t* cl) {
   CTX();
-  if (int st = tg_need(ctx, true)) return st;
-  if (!cl || k < 1 || k > ctx->tg_U) { ctx->err = "trace: the cut k must lie in 1 .. U"; return HDPM_E_ARG; }
-  GUARD({
-    const int N = ctx->tr_N, U = ctx->tg_U;
-    std::vector<int32_t> cut((size_t)U);
-    hdpm::tt_cut(U, ctx->tg_merge.data(), k, cut.data());
-    ctx->d_tg_cutw.ensure((size_t)U);
-    ctx->d_tg_cl.ensure((size_t)N);
-    HIPCHK(hipMemcpyAsync(ctx->d_tg_cutw.p, cut.data(), (size_t)U * 4, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(hdpm::launch_tg_expand(ctx->d_tg_of.p, ctx->d_tg_cutw.p, N, ctx->d_tg_cl.p, ctx->stream));
-    HIPCHK(hipMemcpyAsync(cl, ctx->d_tg_cl.p, (size_t)N * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    return HDPM_OK;
-  })
+  GUARD(return ctx->sum.trace_cut_labels(k, cl);)
 }
 int hdpm_debug_draw(hdpm_ctx* h, const double* logw, int32_t E, double rU, int32_t two_way, int32_t ocml,
                     int32_t* pick) {

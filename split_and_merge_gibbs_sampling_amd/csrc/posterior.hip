@@ -24,6 +24,8 @@
 
 #include <cstdint>
 
+#include "summary_launch.hpp"
+
 namespace hdpm {
 
 constexpr int kPsmTile = 128;

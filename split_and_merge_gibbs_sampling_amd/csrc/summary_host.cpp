@@ -1,0 +1,539 @@
+// summary_host.cpp -- host side of the posterior summaries (summary_host.hpp): the dense
+// psm of posterior.hip, the matrix-free summaries of trace_summary.hip, the uncertainty
+// calls of trace_uncertainty.hip and the average-linkage search of trace_tree.hpp.  The
+// arithmetic that turns the device's integer sums into losses is in trace_loss.hpp.
+#include "summary_host.hpp"
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <utility>
+
+#include "../../include/hdpm.h"
+#include "summary_launch.hpp"
+#include "trace_loss.hpp"
+#include "trace_tree.hpp"
+
+namespace hdpm {
+
+constexpr size_t kTraceBudget = (size_t)256 << 20;      // default table bytes per block of candidates
+constexpr size_t kTraceStageWords = (size_t)16 << 20;   // labels uploaded per block of draws (64 MB)
+
+// ---- the dense psm (posterior.hip)
+int Summaries::psm_build(const int32_t* c_trace, int32_t M, int32_t N) {
+  if (!c_trace || M <= 0 || N <= 0) return HDPM_E_ARG;
+  if (tl_label_max(c_trace, (int64_t)M * N) < 0) { err = "psm: labels must be in 0..254"; return HDPM_E_ARG; }
+  const int Mp = (M + 15) & ~15;
+  d_psm_trace.ensure((size_t)M * N);
+  d_psm_lab.ensure((size_t)N * Mp);
+  d_psm_cnt.ensure((size_t)N * N);
+  HIPCHK(hipMemcpyAsync(d_psm_trace.p, c_trace, (size_t)M * N * 4, hipMemcpyHostToDevice, stream));
+  HIPCHK(launch_psm(d_psm_trace.p, M, N, d_psm_lab.p, d_psm_cnt.p, stream));
+  HIPCHK(hipStreamSynchronize(stream));
+  psm_N = N;
+  psm_M = M;
+  return HDPM_OK;
+}
+int Summaries::psm_rows(int32_t row0, int32_t nrows, double* out) {
+  const int N = psm_N;
+  if (!out || N == 0 || row0 < 0 || nrows < 0 || row0 + nrows > N) return HDPM_E_ARG;
+  std::vector<uint32_t> c((size_t)nrows * N);
+  HIPCHK(hipMemcpyAsync(c.data(), d_psm_cnt.p + (size_t)row0 * N, c.size() * 4, hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipStreamSynchronize(stream));
+  const double M = (double)psm_M;
+  for (size_t q = 0; q < c.size(); ++q) out[q] = (double)c[q] / M;
+  return HDPM_OK;
+}
+int Summaries::psm_vi_lb(const int32_t* cls, int32_t ncand, double* out) {
+  const int N = psm_N;
+  if (!cls || !out || N == 0 || ncand <= 0) return HDPM_E_ARG;
+  d_psm_cls.ensure((size_t)ncand * N);
+  d_psm_all.ensure((size_t)N);
+  d_psm_same.ensure((size_t)ncand * N);
+  HIPCHK(hipMemcpyAsync(d_psm_cls.p, cls, (size_t)ncand * N * 4, hipMemcpyHostToDevice, stream));
+  HIPCHK(launch_vi_terms(d_psm_cnt.p, N, psm_M, d_psm_cls.p, ncand, d_psm_all.p, d_psm_same.p, stream));
+  std::vector<double> all((size_t)N);
+  std::vector<double> same((size_t)ncand * N);
+  HIPCHK(hipMemcpyAsync(all.data(), d_psm_all.p, all.size() * 8, hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipMemcpyAsync(same.data(), d_psm_same.p, same.size() * 8, hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipStreamSynchronize(stream));
+  std::vector<int> sz;
+  for (int c = 0; c < ncand; ++c) {
+    const int32_t* cl = cls + (size_t)c * N;
+    int mx = 0;
+    for (int i = 0; i < N; ++i) mx = std::max(mx, cl[i]);
+    sz.assign((size_t)mx + 1, 0);
+    for (int i = 0; i < N; ++i) {
+      if (cl[i] < 0) { err = "psm: negative cluster label"; return HDPM_E_ARG; }
+      sz[cl[i]]++;
+    }
+    double f = 0.0;
+    for (int i = 0; i < N; ++i)
+      f = f + tl_vi_lb_term(std::log2((double)sz[cl[i]]), std::log2(all[i]), std::log2(same[(size_t)c * N + i]), N);
+    out[c] = f;
+  }
+  return HDPM_OK;
+}
+
+// ---- matrix-free posterior summary (trace_summary.hip): shared by the trace_* calls
+// what a call needs to have been made before it
+int Summaries::need(bool groups, bool tree) {
+  if (tr_N == 0) { err = "trace: hdpm_trace_build has not been called"; return HDPM_E_ARG; }
+  if (groups && tg_U == 0) { err = "trace: hdpm_trace_groups has not been called"; return HDPM_E_ARG; }
+  if (tree && !tg_tree) { err = "trace: hdpm_trace_avg_tree has not been called"; return HDPM_E_ARG; }
+  return HDPM_OK;
+}
+
+// the candidates' labels checked (0..254); *Ka = the largest cluster count among them
+int Summaries::check(const int32_t* cls, int ncand, int* Ka) {
+  if (int st = need(false, false)) return st;
+  if (!cls || ncand <= 0) { err = "trace: no candidate partitions"; return HDPM_E_ARG; }
+  const int mx = tl_label_max(cls, (int64_t)ncand * tr_N);
+  if (mx < 0) { err = "trace: candidate labels must be in 0..254"; return HDPM_E_ARG; }
+  *Ka = mx + 1;
+  return HDPM_OK;
+}
+
+// A set of candidate partitions: of the points (cls: count x N labels, rows of Np bytes
+// against the label bytes of the draws) or, with cls == nullptr, the cuts of the tree into
+// k0, k0 + 1, ... clusters (one label per group of equal label columns, rows of Up bytes
+// against the groups' signatures, weighted by the groups' sizes).
+struct Summaries::Cands {
+  const int32_t* cls;
+  int k0, count;
+};
+
+// The candidates in blocks of at most budget / (M x Ka x Kz x 4) (and kTraceMaxBlock): their
+// tables, then the per-entry sums (terms; `all` with the first block if want_all) and the
+// per-candidate reductions (reduce); f(c0, nc, rows) runs with the block's results on the
+// device and the block's label bytes in rows.  A candidate's results do not depend on the
+// block it falls in.
+template <class F>
+void Summaries::blocks(Cands cd, int Ka, bool terms, bool want_all, bool reduce, F f) {
+  const bool cuts = !cd.cls;
+  const int M = tr_M, Kz = tr_Kz, n = cuts ? tg_U : tr_N, width = cuts ? tg_Up : tr_Np;
+  DevBuf<uint8_t>& d_rows = cuts ? d_tg_cut : d_tr_cls;
+  DevBuf<uint64_t>& d_all = cuts ? d_tg_all : d_tr_all;
+  DevBuf<uint64_t>& d_same = cuts ? d_tg_same : d_tr_same;
+  if (!cuts && want_all && !terms && !reduce) {
+    // `all` alone needs the draws' sizes only: no tables, no candidate on the device; the
+    // gather runs its sizes row (candidate count 0) and f sees an empty first block
+    d_tr_all.ensure((size_t)tr_N);
+    HIPCHK(launch_tr_gather(d_tr_lab.p, nullptr, tr_N, tr_Np, M, 0, Ka, Kz, nullptr, d_tr_sizes.p, d_tr_all.p, nullptr,
+                            stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    f(0, 0, nullptr);
+    return;
+  }
+  const size_t per = (size_t)M * Ka * Kz;
+  const size_t cb = tl_block(tr_budget, per, (size_t)cd.count);
+  d_rows.ensure(cb * width);
+  d_tr_tab.ensure(cb * per);
+  if (terms) d_same.ensure(cb * n);
+  if (want_all) d_all.ensure((size_t)n);
+  if (reduce) {
+    d_tr_q1.ensure(cb * M);
+    d_tr_l1.ensure(cb * M);
+    d_tr_q.ensure(cb);
+    d_tr_l.ensure(cb);
+  }
+  std::vector<uint8_t> bytes(cb * width);
+  std::vector<int32_t> cut(cuts ? (size_t)n : 0);
+  for (int c0 = 0; c0 < cd.count; c0 += (int)cb) {
+    const int nc = std::min((int)cb, cd.count - c0);
+    std::memset(bytes.data(), 0xFF, bytes.size());
+    for (int c = 0; c < nc; ++c) {
+      if (cuts) tt_cut(n, tg_merge.data(), cd.k0 + c0 + c, cut.data());
+      const int32_t* cl = cuts ? cut.data() : cd.cls + (size_t)(c0 + c) * n;
+      uint8_t* row = bytes.data() + (size_t)c * width;
+      for (int i = 0; i < n; ++i) row[i] = (uint8_t)cl[i];
+    }
+    HIPCHK(hipMemcpyAsync(d_rows.p, bytes.data(), (size_t)nc * width, hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemsetAsync(d_tr_tab.p, 0, (size_t)nc * per * 4, stream));
+    uint64_t* all = want_all && c0 == 0 ? d_all.p : nullptr;
+    if (cuts) {
+      HIPCHK(launch_tg_tables(d_tg_sigT.p, d_rows.p, d_tg_w.p, n, width, M, nc, Ka, Kz, d_tr_tab.p, stream));
+      if (terms)
+        HIPCHK(launch_tg_gather(d_tg_sigT.p, d_rows.p, n, width, M, nc, Ka, Kz, d_tr_tab.p, d_tr_sizes.p, all,
+                                d_same.p, stream));
+    } else {
+      HIPCHK(launch_tr_tables(d_tr_lab.p, d_rows.p, width, M, nc, Ka, Kz, d_tr_tab.p, stream));
+      if (terms)
+        HIPCHK(launch_tr_gather(d_tr_lab.p, d_rows.p, n, width, M, nc, Ka, Kz, d_tr_tab.p, d_tr_sizes.p, all,
+                                d_same.p, stream));
+    }
+    if (reduce) HIPCHK(launch_tr_reduce(d_tr_tab.p, nc, M, Ka * Kz, d_tr_q1.p, d_tr_l1.p, d_tr_q.p, d_tr_l.p, stream));
+    // the point candidates' f finds the stream drained; the cuts' f queues its copies behind
+    // the block and waits once
+    if (!cuts) HIPCHK(hipStreamSynchronize(stream));
+    f(c0, nc, bytes.data());
+  }
+}
+
+// The losses of a set of candidates (trace_losses, trace_cut_losses).  VI.lb sums one term
+// per point: over the points in double and index order (the terms on the host's threads,
+// as psm_vi_lb sums them), over the groups weighted by their sizes in long double (the few
+// groups' terms on the calling thread).
+void Summaries::losses(Cands cd, int Ka, double* vi_lb, double* vi, uint64_t* binder_A, uint64_t* binder_Q) {
+  const bool cuts = !cd.cls, terms = vi_lb != nullptr, reduce = vi || binder_Q;
+  const int N = tr_N, n = cuts ? tg_U : N, width = cuts ? tg_Up : tr_Np;
+  const double dM = (double)tr_M;
+  std::vector<uint64_t> all, same, q, sz((size_t)Ka);
+  std::vector<double> l, lall, term, lsz((size_t)Ka);
+  auto each = [&](auto body) {
+    if (cuts) body(0, n);
+    else parallel_for(n, body);
+  };
+  blocks(cd, Ka, terms, terms, reduce, [&](int c0, int nc, const uint8_t* rows) {
+    if (terms) {
+      if (c0 == 0) {
+        all.resize((size_t)n);
+        HIPCHK(hipMemcpyAsync(all.data(), (cuts ? d_tg_all : d_tr_all).p, (size_t)n * 8, hipMemcpyDeviceToHost,
+                              stream));
+      }
+      same.resize((size_t)nc * n);
+      HIPCHK(hipMemcpyAsync(same.data(), (cuts ? d_tg_same : d_tr_same).p, same.size() * 8, hipMemcpyDeviceToHost,
+                            stream));
+    }
+    if (reduce) {
+      q.resize((size_t)nc);
+      l.resize((size_t)nc);
+      HIPCHK(hipMemcpyAsync(q.data(), d_tr_q.p, (size_t)nc * 8, hipMemcpyDeviceToHost, stream));
+      HIPCHK(hipMemcpyAsync(l.data(), d_tr_l.p, (size_t)nc * 8, hipMemcpyDeviceToHost, stream));
+    }
+    HIPCHK(hipStreamSynchronize(stream));
+    if (terms && c0 == 0) {
+      // log2 sum_j psm_ij is the same for every candidate
+      lall.resize((size_t)n);
+      term.resize((size_t)n);
+      each([&](int64_t i0, int64_t i1) {
+        for (int64_t i = i0; i < i1; ++i) lall[i] = std::log2((double)all[i] / dM);
+      });
+    }
+    for (int c = 0; c < nc; ++c) {
+      const uint8_t* cl = rows + (size_t)c * width;
+      std::fill(sz.begin(), sz.end(), 0);
+      for (int i = 0; i < n; ++i) sz[cl[i]] += cuts ? tg_w[i] : 1;
+      const TlSizes s = tl_sizes(sz.data(), Ka, lsz.data());
+      if (terms) {
+        // the expression of psm_vi_lb, with psm sums = integer sums / M
+        const uint64_t* sm = same.data() + (size_t)c * n;
+        each([&](int64_t i0, int64_t i1) {
+          for (int64_t i = i0; i < i1; ++i)
+            term[i] = tl_vi_lb_term(lsz[cl[i]], lall[i], std::log2((double)sm[i] / dM), N);
+        });
+        double f = 0.0;
+        long double fw = 0.0L;
+        if (cuts) for (int i = 0; i < n; ++i) fw += (long double)tg_w[i] * (long double)term[i];
+        else for (int i = 0; i < n; ++i) f = f + term[i];
+        vi_lb[c0 + c] = cuts ? (double)fw : f;
+      }
+      if (vi) vi[c0 + c] = tl_vi(s.hc, tr_S, l[c], dM, N);
+      if (binder_A) binder_A[c0 + c] = s.A;
+      if (binder_Q) binder_Q[c0 + c] = q[c];
+    }
+  });
+}
+
+int Summaries::trace_build(const int32_t* c_trace, int32_t M, int32_t N, int64_t table_budget_bytes) {
+  if (!c_trace || M <= 0 || N <= 0 || table_budget_bytes < 0) { err = "trace: bad arguments"; return HDPM_E_ARG; }
+  const int mx = tl_label_max(c_trace, (int64_t)M * N);
+  if (mx < 0) { err = "trace: labels must be in 0..254"; return HDPM_E_ARG; }
+  tr_N = 0;   // no trace until this one is complete
+  tg_U = 0;   // and no groups or tree of the previous one
+  tg_counts = tg_tree = false;
+  const int Np = (int)(((int64_t)N + 15) & ~(int64_t)15);
+  d_tr_lab.ensure((size_t)M * Np);
+  d_tr_sizes.ensure((size_t)M * 256);
+  d_tr_q1.ensure((size_t)M);
+  d_tr_l1.ensure((size_t)M);
+  d_tr_q.ensure(1);
+  d_tr_l.ensure(1);
+  {
+    // the int32 labels go up in blocks of draws through one staging buffer, freed at the end
+    const int mb = (int)std::min<size_t>((size_t)M, std::max<size_t>(1, kTraceStageWords / (size_t)N));
+    DevBuf<int32_t> stage;
+    stage.ensure((size_t)mb * N);
+    for (int m0 = 0; m0 < M; m0 += mb) {
+      const int nm = std::min(mb, M - m0);
+      HIPCHK(hipMemcpyAsync(stage.p, c_trace + (size_t)m0 * N, (size_t)nm * N * 4, hipMemcpyHostToDevice, stream));
+      HIPCHK(launch_tr_pack(stage.p, nm, N, Np, d_tr_lab.p + (size_t)m0 * Np, stream));
+    }
+    HIPCHK(hipStreamSynchronize(stream));
+  }
+  HIPCHK(hipMemsetAsync(d_tr_sizes.p, 0, (size_t)M * 256 * 4, stream));
+  HIPCHK(launch_tr_sizes(d_tr_lab.p, Np, M, d_tr_sizes.p, stream));
+  HIPCHK(launch_tr_reduce(d_tr_sizes.p, 1, M, 256, d_tr_q1.p, d_tr_l1.p, d_tr_q.p, d_tr_l.p, stream));
+  HIPCHK(hipMemcpyAsync(&tr_P, d_tr_q.p, 8, hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipMemcpyAsync(&tr_S, d_tr_l.p, 8, hipMemcpyDeviceToHost, stream));
+  // the per-draw P_m and S_m stay on the host (later calls reuse d_tr_q1 / d_tr_l1), with
+  // the draws' cluster counts from the size rows
+  tr_Pm.resize((size_t)M);
+  tr_Sm.resize((size_t)M);
+  tr_Km.assign((size_t)M, 0);
+  std::vector<uint32_t> sizes((size_t)M * 256);
+  HIPCHK(hipMemcpyAsync(tr_Pm.data(), d_tr_q1.p, (size_t)M * 8, hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipMemcpyAsync(tr_Sm.data(), d_tr_l1.p, (size_t)M * 8, hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipMemcpyAsync(sizes.data(), d_tr_sizes.p, sizes.size() * 4, hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipStreamSynchronize(stream));
+  for (int m = 0; m < M; ++m)
+    for (int b = 0; b < 256; ++b) tr_Km[m] += sizes[(size_t)m * 256 + b] != 0u;
+  tr_M = M;
+  tr_Np = Np;
+  tr_Kz = mx + 1;
+  tr_budget = table_budget_bytes > 0 ? (size_t)table_budget_bytes : kTraceBudget;
+  tr_N = N;
+  return HDPM_OK;
+}
+int Summaries::trace_terms(const int32_t* cls, int32_t ncand, uint64_t* all, uint64_t* same) {
+  int Ka = 0;
+  if (int st = check(cls, ncand, &Ka)) return st;
+  if (!all && !same) return HDPM_OK;
+  const size_t N = (size_t)tr_N;
+  blocks({cls, 0, ncand}, Ka, same != nullptr, all != nullptr, false, [&](int c0, int nc, const uint8_t*) {
+    if (all && c0 == 0) HIPCHK(hipMemcpyAsync(all, d_tr_all.p, N * 8, hipMemcpyDeviceToHost, stream));
+    if (same)
+      HIPCHK(hipMemcpyAsync(same + (size_t)c0 * N, d_tr_same.p, (size_t)nc * N * 8, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+  });
+  return HDPM_OK;
+}
+int Summaries::trace_losses(const int32_t* cls, int32_t ncand, double* vi_lb, double* vi, uint64_t* binder_Q,
+                            uint64_t* binder_P) {
+  int Ka = 0;
+  if (int st = check(cls, ncand, &Ka)) return st;
+  if (binder_P) *binder_P = tr_P;
+  if (vi_lb || vi || binder_Q) losses({cls, 0, ncand}, Ka, vi_lb, vi, nullptr, binder_Q);
+  return HDPM_OK;
+}
+int Summaries::trace_tables(const int32_t* cls, int32_t ncand, int32_t m0, int32_t nm, uint32_t* out) {
+  int Ka = 0;
+  if (int st = check(cls, ncand, &Ka)) return st;
+  if (!out || m0 < 0 || nm <= 0 || (int64_t)m0 + nm > tr_M) {
+    err = "trace: draws m0 .. m0 + nm - 1 must lie in 0 .. M - 1";
+    return HDPM_E_ARG;
+  }
+  const int M = tr_M, Kz = tr_Kz;
+  const size_t cells = (size_t)Ka * Kz;
+  std::memset(out, 0, (size_t)ncand * nm * 65536 * 4);
+  std::vector<uint32_t> t((size_t)nm * cells);
+  blocks({cls, 0, ncand}, Ka, false, false, false, [&](int c0, int nc, const uint8_t*) {
+    for (int c = 0; c < nc; ++c) {
+      HIPCHK(hipMemcpyAsync(t.data(), d_tr_tab.p + ((size_t)c * M + m0) * cells, t.size() * 4, hipMemcpyDeviceToHost,
+                            stream));
+      HIPCHK(hipStreamSynchronize(stream));
+      for (int m = 0; m < nm; ++m)
+        for (int a = 0; a < Ka; ++a)
+          std::memcpy(out + (((size_t)(c0 + c) * nm + m) * 256 + a) * 256, t.data() + ((size_t)m * Ka + a) * Kz,
+                      (size_t)Kz * 4);
+    }
+  });
+  return HDPM_OK;
+}
+
+// ---- how far the estimate can be trusted (trace_uncertainty.hip)
+int Summaries::trace_distances(const int32_t* cls, int32_t ncand, double* vi, uint64_t* binder, int32_t* draw_k) {
+  int Ka = 0;
+  if (int st = check(cls, ncand, &Ka)) return st;
+  const int N = tr_N, M = tr_M;
+  if (draw_k) std::memcpy(draw_k, tr_Km.data(), (size_t)M * 4);
+  if (!vi && !binder) return HDPM_OK;
+  std::vector<uint64_t> q1, sz((size_t)Ka);
+  std::vector<double> l1, lsz((size_t)Ka);
+  // the per-(candidate, draw) sums of k_tr_reduce, as they stand before k_tr_reduce_draws
+  blocks({cls, 0, ncand}, Ka, false, false, true, [&](int c0, int nc, const uint8_t* rows) {
+    q1.resize((size_t)nc * M);
+    l1.resize((size_t)nc * M);
+    HIPCHK(hipMemcpyAsync(q1.data(), d_tr_q1.p, q1.size() * 8, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipMemcpyAsync(l1.data(), d_tr_l1.p, l1.size() * 8, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    for (int c = 0; c < nc; ++c) {
+      const uint8_t* cl = rows + (size_t)c * tr_Np;
+      std::fill(sz.begin(), sz.end(), 0);
+      for (int i = 0; i < N; ++i) sz[cl[i]]++;
+      const TlSizes s = tl_sizes(sz.data(), Ka, lsz.data());
+      for (int m = 0; m < M; ++m) {
+        const size_t o = (size_t)(c0 + c) * M + m, k = (size_t)c * M + m;
+        if (vi) vi[o] = tl_vi_draw(s.hc, tr_Sm[m], l1[k], N);
+        if (binder) binder[o] = s.A + tr_Pm[m] - 2 * q1[k];
+      }
+    }
+  });
+  return HDPM_OK;
+}
+int Summaries::trace_affinity(const int32_t* cl, int32_t Ka, uint64_t* aff, uint64_t* cross) {
+  int used = 0;   // the largest label + 1
+  if (int st = check(cl, 1, &used)) return st;
+  if (Ka < 1 || Ka > 255) { err = "trace: Ka must be in 1..255"; return HDPM_E_ARG; }
+  if (used > Ka) { err = "trace: the partition's labels must be in 0..Ka-1"; return HDPM_E_ARG; }
+  const int N = tr_N, Np = tr_Np, M = tr_M, Kz = tr_Kz;
+  if (cross && !tl_fits63((uint64_t)N, (uint64_t)M)) {
+    err = "trace: N^2 M does not fit 63 bits: the sums of cross would overflow";
+    return HDPM_E_ARG;
+  }
+  if (!aff && !cross) return HDPM_OK;
+  // one candidate always fits a block: its tables, then their transpose
+  blocks({cl, 0, 1}, Ka, false, false, false, [&](int, int, const uint8_t*) {
+    const size_t per = (size_t)M * Ka * Kz;
+    d_tr_tabT.ensure(per);
+    HIPCHK(launch_tr_transpose(d_tr_tab.p, M, Ka, Kz, d_tr_tabT.p, stream));
+    if (cross) {
+      d_tr_cross.ensure((size_t)Ka * Ka);
+      HIPCHK(hipMemsetAsync(d_tr_cross.p, 0, (size_t)Ka * Ka * 8, stream));
+      HIPCHK(launch_tr_cross(d_tr_tabT.p, M, Ka, Kz, d_tr_cross.p, stream));
+      HIPCHK(hipMemcpyAsync(cross, d_tr_cross.p, (size_t)Ka * Ka * 8, hipMemcpyDeviceToHost, stream));
+    }
+    if (aff) {
+      // blocks of points: the staging (pb x Ka x 8 bytes) within the table budget, in whole
+      // groups of 16 points and at least one; each block goes to the caller as it completes
+      size_t pb = (tr_budget / ((size_t)Ka * 8)) & ~(size_t)15;
+      pb = std::min(std::max<size_t>(pb, 16), (size_t)Np);
+      d_tr_aff.ensure(pb * Ka);
+      for (int64_t i0 = 0; i0 < N; i0 += (int64_t)pb) {
+        const int np = (int)std::min<int64_t>((int64_t)pb, N - i0);
+        HIPCHK(launch_tr_affinity(d_tr_lab.p, Np, M, Ka, Kz, d_tr_tabT.p, (int)i0, np, d_tr_aff.p, stream));
+        HIPCHK(hipMemcpyAsync(aff + (size_t)i0 * Ka, d_tr_aff.p, (size_t)np * Ka * 8, hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+      }
+    }
+    HIPCHK(hipStreamSynchronize(stream));
+  });
+  return HDPM_OK;
+}
+
+// ---- average-linkage search on the groups of equal label columns (trace_summary.hip k_tg_*,
+// trace_tree.hpp)
+void Summaries::group_counts() {
+  if (tg_counts) return;
+  const size_t U = (size_t)tg_U;
+  d_tg_S.ensure(U * U);
+  HIPCHK(launch_tg_counts(d_tg_sig.p, tg_U, tr_M, tg_Mp, d_tg_S.p, stream));
+  HIPCHK(hipStreamSynchronize(stream));
+  tg_counts = true;
+}
+int Summaries::trace_groups(int32_t max_groups, int32_t hash_bits, int32_t* U_out) {
+  if (int st = need(false, false)) return st;
+  if (max_groups == 0) max_groups = HDPM_TRACE_GROUPS_DEFAULT;
+  if (max_groups < 0 || max_groups > HDPM_TRACE_GROUPS_MAX || hash_bits < 0 || hash_bits > 32) {
+    err = "trace: max_groups must be in 1.." + std::to_string(HDPM_TRACE_GROUPS_MAX) + " and hash_bits in 0..32";
+    return HDPM_E_ARG;
+  }
+  const int N = tr_N, Np = tr_Np, M = tr_M;
+  if (!tl_fits63((uint64_t)N, (uint64_t)M)) {
+    err = "trace: N^2 M does not fit 63 bits: the tree's integer sums would overflow";
+    return HDPM_E_ARG;
+  }
+  tg_U = 0;
+  tg_counts = tg_tree = false;
+  uint32_t T = 1024;
+  while (T < 4u * (uint32_t)max_groups) T <<= 1;
+  d_tg_rep.ensure(T);
+  d_tg_slotfirst.ensure(T);
+  d_tg_slotgid.ensure(T);
+  d_tg_pslot.ensure((size_t)N);
+  d_tg_ctl.ensure(2);
+  HIPCHK(hipMemsetAsync(d_tg_rep.p, 0xFF, (size_t)T * 4, stream));
+  HIPCHK(hipMemsetAsync(d_tg_slotfirst.p, 0xFF, (size_t)T * 4, stream));
+  HIPCHK(hipMemsetAsync(d_tg_ctl.p, 0, 8, stream));
+  HIPCHK(launch_tg_insert(d_tr_lab.p, N, Np, M, hash_bits, T, (uint32_t)max_groups, d_tg_rep.p, d_tg_slotfirst.p,
+                          d_tg_pslot.p, d_tg_ctl.p, stream));
+  uint32_t ctl[2] = {0u, 0u};
+  std::vector<uint32_t> sf((size_t)T);
+  HIPCHK(hipMemcpyAsync(ctl, d_tg_ctl.p, 8, hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipMemcpyAsync(sf.data(), d_tg_slotfirst.p, (size_t)T * 4, hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipStreamSynchronize(stream));
+  if (ctl[1]) {
+    err = "trace: more than max_groups = " + std::to_string(max_groups) +
+          " distinct label columns: the trace is too unsettled for the average-linkage search";
+    return HDPM_E_ARG;
+  }
+  // the groups numbered by ascending smallest member: whichever slot a column landed in
+  std::vector<std::pair<uint32_t, uint32_t>> order;
+  for (uint32_t s = 0; s < T; ++s)
+    if (sf[s] != 0xFFFFFFFFu) order.emplace_back(sf[s], s);
+  std::sort(order.begin(), order.end());
+  const int U = (int)order.size();
+  if (U == 0 || (uint32_t)U != ctl[0]) { err = "trace: the group table is inconsistent"; return HDPM_E_DEVICE; }
+  std::vector<uint32_t> gid((size_t)T, 0u);
+  tg_first.resize((size_t)U);
+  for (int u = 0; u < U; ++u) {
+    tg_first[u] = order[u].first;
+    gid[order[u].second] = (uint32_t)u;
+  }
+  const int Mp = (M + 63) & ~63, Up = (U + 15) & ~15;
+  d_tg_of.ensure((size_t)N);
+  d_tg_first.ensure((size_t)U);
+  d_tg_w.ensure((size_t)U);
+  d_tg_sig.ensure((size_t)U * Mp);
+  d_tg_sigT.ensure((size_t)M * Up);
+  HIPCHK(hipMemcpyAsync(d_tg_slotgid.p, gid.data(), (size_t)T * 4, hipMemcpyHostToDevice, stream));
+  HIPCHK(hipMemcpyAsync(d_tg_first.p, tg_first.data(), (size_t)U * 4, hipMemcpyHostToDevice, stream));
+  HIPCHK(hipMemsetAsync(d_tg_w.p, 0, (size_t)U * 4, stream));
+  HIPCHK(launch_tg_finish(d_tr_lab.p, N, Np, M, U, Mp, Up, d_tg_pslot.p, d_tg_slotgid.p, d_tg_first.p, d_tg_of.p,
+                          d_tg_w.p, d_tg_sig.p, d_tg_sigT.p, stream));
+  tg_w.resize((size_t)U);
+  HIPCHK(hipMemcpyAsync(tg_w.data(), d_tg_w.p, (size_t)U * 4, hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipStreamSynchronize(stream));
+  tg_Mp = Mp;
+  tg_Up = Up;
+  tg_U = U;
+  if (U_out) *U_out = U;
+  return HDPM_OK;
+}
+int Summaries::trace_group_info(int32_t* first, int32_t* weight, int32_t* group_of, uint32_t* counts) {
+  if (int st = need(true, false)) return st;
+  const size_t U = (size_t)tg_U;
+  if (first) std::memcpy(first, tg_first.data(), U * 4);
+  if (weight) std::memcpy(weight, tg_w.data(), U * 4);
+  if (group_of) HIPCHK(hipMemcpyAsync(group_of, d_tg_of.p, (size_t)tr_N * 4, hipMemcpyDeviceToHost, stream));
+  if (counts) {
+    group_counts();
+    HIPCHK(hipMemcpyAsync(counts, d_tg_S.p, U * U * 4, hipMemcpyDeviceToHost, stream));
+  }
+  HIPCHK(hipStreamSynchronize(stream));
+  return HDPM_OK;
+}
+int Summaries::trace_avg_tree(int32_t* merge, double* height) {
+  if (int st = need(true, false)) return st;
+  const size_t U = (size_t)tg_U;
+  if (!tg_tree) {
+    group_counts();
+    std::vector<uint32_t> S(U * U);
+    HIPCHK(hipMemcpyAsync(S.data(), d_tg_S.p, U * U * 4, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    std::vector<uint64_t> w(tg_w.begin(), tg_w.end()), first(tg_first.begin(), tg_first.end());
+    tg_merge.assign((U - 1) * 2, 0);
+    tg_height.assign(U - 1, 0.0);
+    tt_avg_linkage((int)U, w.data(), first.data(), S.data(), (uint64_t)tr_M, tg_merge.data(), tg_height.data());
+    tg_tree = true;
+  }
+  if (merge && U > 1) std::memcpy(merge, tg_merge.data(), (U - 1) * 2 * 4);
+  if (height && U > 1) std::memcpy(height, tg_height.data(), (U - 1) * 8);
+  return HDPM_OK;
+}
+int Summaries::trace_cut_losses(int32_t k0, int32_t nk, double* vi_lb, double* vi, uint64_t* binder_A,
+                                uint64_t* binder_Q) {
+  if (int st = need(true, true)) return st;
+  if (k0 < 1 || nk < 1 || (int64_t)k0 + nk - 1 > std::min(tg_U, 255)) {
+    err = "trace: cuts k0 .. k0 + nk - 1 must lie in 1 .. min(U, 255)";
+    return HDPM_E_ARG;
+  }
+  if (vi_lb || vi || binder_A || binder_Q) losses({nullptr, k0, nk}, k0 + nk - 1, vi_lb, vi, binder_A, binder_Q);
+  return HDPM_OK;
+}
+int Summaries::trace_cut_labels(int32_t k, int32_t* cl) {
+  if (int st = need(true, true)) return st;
+  if (!cl || k < 1 || k > tg_U) { err = "trace: the cut k must lie in 1 .. U"; return HDPM_E_ARG; }
+  const int N = tr_N, U = tg_U;
+  std::vector<int32_t> cut((size_t)U);
+  tt_cut(U, tg_merge.data(), k, cut.data());
+  d_tg_cutw.ensure((size_t)U);
+  d_tg_cl.ensure((size_t)N);
+  HIPCHK(hipMemcpyAsync(d_tg_cutw.p, cut.data(), (size_t)U * 4, hipMemcpyHostToDevice, stream));
+  HIPCHK(launch_tg_expand(d_tg_of.p, d_tg_cutw.p, N, d_tg_cl.p, stream));
+  HIPCHK(hipMemcpyAsync(cl, d_tg_cl.p, (size_t)N * 4, hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipStreamSynchronize(stream));
+  return HDPM_OK;
+}
+
+}  // namespace hdpm

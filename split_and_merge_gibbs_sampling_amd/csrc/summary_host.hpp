@@ -1,0 +1,88 @@
+// summary_host.hpp -- the posterior summaries of a context: the state and host logic behind
+// hdpm_psm_* (posterior.hip) and hdpm_trace_* (trace_summary.hip, trace_uncertainty.hip).
+//
+// The summaries work on saved labels and never touch chain state: of their context they use
+// the main stream and the error string, bound at construction.  Every method is the body of
+// the C call of the same name (include/hdpm.h) and returns its HDPM_* status; HIP errors
+// leave as HipError, for the caller's guard.
+#pragma once
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "host_util.hpp"
+
+namespace hdpm {
+
+class Summaries {
+ public:
+  Summaries(hipStream_t& stream, std::string& err) : stream(stream), err(err) {}
+
+  int psm_build(const int32_t* c_trace, int32_t M, int32_t N);
+  int psm_rows(int32_t row0, int32_t nrows, double* out);
+  int psm_vi_lb(const int32_t* cls, int32_t ncand, double* out);
+
+  int trace_build(const int32_t* c_trace, int32_t M, int32_t N, int64_t table_budget_bytes);
+  int trace_terms(const int32_t* cls, int32_t ncand, uint64_t* all, uint64_t* same);
+  int trace_losses(const int32_t* cls, int32_t ncand, double* vi_lb, double* vi, uint64_t* binder_Q,
+                   uint64_t* binder_P);
+  int trace_tables(const int32_t* cls, int32_t ncand, int32_t m0, int32_t nm, uint32_t* out);
+  int trace_distances(const int32_t* cls, int32_t ncand, double* vi, uint64_t* binder, int32_t* draw_k);
+  int trace_affinity(const int32_t* cl, int32_t Ka, uint64_t* aff, uint64_t* cross);
+  int trace_groups(int32_t max_groups, int32_t hash_bits, int32_t* U_out);
+  int trace_group_info(int32_t* first, int32_t* weight, int32_t* group_of, uint32_t* counts);
+  int trace_avg_tree(int32_t* merge, double* height);
+  int trace_cut_losses(int32_t k0, int32_t nk, double* vi_lb, double* vi, uint64_t* binder_A, uint64_t* binder_Q);
+  int trace_cut_labels(int32_t k, int32_t* cl);
+
+ private:
+  hipStream_t& stream;
+  std::string& err;
+
+  // hdpm_psm_*: label bytes, co-clustering counts, VI.lb sums
+  DevBuf<int32_t> d_psm_trace, d_psm_cls;
+  DevBuf<uint8_t> d_psm_lab;
+  DevBuf<uint32_t> d_psm_cnt;
+  DevBuf<double> d_psm_all, d_psm_same;
+  int psm_N = 0, psm_M = 0;
+  // hdpm_trace_*: label bytes (M x Np), cluster sizes of the draws (M x 256), and per block
+  // of candidates their label bytes, contingency tables (nc x M x Ka x Kz), per-point sums
+  // and per-draw / per-candidate reductions
+  DevBuf<uint8_t> d_tr_lab, d_tr_cls;
+  DevBuf<uint32_t> d_tr_sizes, d_tr_tab;
+  DevBuf<uint64_t> d_tr_all, d_tr_same, d_tr_q1, d_tr_q;
+  DevBuf<double> d_tr_l1, d_tr_l;
+  int tr_N = 0, tr_M = 0, tr_Np = 0, tr_Kz = 0;
+  size_t tr_budget = 0;
+  uint64_t tr_P = 0;     // sum_m sum_b C2(n^m_b)
+  double tr_S = 0.0;     // sum_m sum_b n^m_b log2 n^m_b
+  // per draw (trace_distances): P_m, S_m and the cluster count; the estimate's tables
+  // transposed, the staging of one block of points of aff, and cross (trace_affinity)
+  std::vector<uint64_t> tr_Pm;
+  std::vector<double> tr_Sm;
+  std::vector<int32_t> tr_Km;
+  DevBuf<uint32_t> d_tr_tabT;
+  DevBuf<uint64_t> d_tr_aff, d_tr_cross;
+  // groups of equal label columns and their average-linkage tree (trace_groups ..
+  // trace_cut_labels): the open-addressing table, group_of per point, the groups'
+  // signatures both ways round, S (U x U) once it is first needed, the tree on the host
+  DevBuf<uint32_t> d_tg_rep, d_tg_slotfirst, d_tg_pslot, d_tg_ctl, d_tg_slotgid, d_tg_of, d_tg_first, d_tg_w, d_tg_S;
+  DevBuf<uint8_t> d_tg_sig, d_tg_sigT, d_tg_cut;
+  DevBuf<uint64_t> d_tg_all, d_tg_same;
+  DevBuf<int32_t> d_tg_cl, d_tg_cutw;
+  int tg_U = 0, tg_Mp = 0, tg_Up = 0;
+  bool tg_counts = false, tg_tree = false;
+  std::vector<uint32_t> tg_first, tg_w;
+  std::vector<int32_t> tg_merge;
+  std::vector<double> tg_height;
+
+  struct Cands;
+  int need(bool groups, bool tree);
+  int check(const int32_t* cls, int ncand, int* Ka);
+  template <class F>
+  void blocks(Cands cd, int Ka, bool terms, bool want_all, bool reduce, F f);
+  void losses(Cands cd, int Ka, double* vi_lb, double* vi, uint64_t* binder_A, uint64_t* binder_Q);
+  void group_counts();
+};
+
+}  // namespace hdpm

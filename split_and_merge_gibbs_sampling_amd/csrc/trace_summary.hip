@@ -33,6 +33,8 @@
 #include <algorithm>
 #include <cstdint>
 
+#include "summary_launch.hpp"
+
 namespace hdpm {
 
 constexpr int kTrThreads = 256;

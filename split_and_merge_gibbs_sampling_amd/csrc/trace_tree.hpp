@@ -22,7 +22,7 @@
 // settled trace have the lowest indices, so the many light groups above them never rescan
 // when a heavy group grows: O(U^2) there, O(U^3) at worst.
 //
-// Plain C++, no HIP: engine.cpp includes it, and tests/cpp/trace_tree_test.cpp checks it on
+// Plain C++, no HIP: summary_host.cpp includes it, and tests/cpp/trace_tree_test.cpp checks it on
 // the host against an O(U^3) loop.
 #pragma once
 #include <cstddef>

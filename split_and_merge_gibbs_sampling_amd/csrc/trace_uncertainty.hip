@@ -32,6 +32,8 @@
 #include <algorithm>
 #include <cstdint>
 
+#include "summary_launch.hpp"
+
 namespace hdpm {
 
 constexpr int kTuThreads = 256;
