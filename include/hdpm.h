@@ -553,6 +553,52 @@ int hdpm_trace_avg_tree(hdpm_ctx* ctx, int32_t* merge, double* height);
 int hdpm_trace_cut_losses(hdpm_ctx* ctx, int32_t k0, int32_t nk, double* vi_lb, double* vi, uint64_t* binder_A,
                           uint64_t* binder_Q);
 int hdpm_trace_cut_labels(hdpm_ctx* ctx, int32_t k, int32_t* cl);
+/* The posterior predictive from the recorded draws: where a row the chain never saw belongs,
+ * and the pointwise log-likelihood of the training rows for WAIC and LPML.  Saved draw s
+ * (0 <= s < M) has K_s clusters of sizes n_k (from the saved labels), centers c_kj and sigmas
+ * sg_kj; gamma and attrisize m_j are the chain's; a row y holds codes 1..m_j.  With
+ *   ll_k(y) = sum_j dhamming(y_j, c_kj, sg_kj, m_j), added in attribute order (the bits of
+ *             hdpm_loglik_matrix on that state),
+ *   ll_0 = -sum_j log(m_j), the log prior predictive of any row (a uniform prior center, and
+ *          dhamming sums to 1 over the codes for every sigma),
+ *   w_k = log n_k + ll_k(y), w_0 = log gamma + ll_0 (the urn given draw s), lse = log sum_{k >= 0}
+ *   exp(w_k) and r_k = exp(w_k - lse):
+ * the calls below come after hdpm_trace_build of the same saved iterations, whose labels of
+ * draw s must be exactly 0..K_s-1 (label k names parameter row k); a later hdpm_trace_build
+ * discards the parameters.  Every exp and log is glibc's on host and device; every sum of
+ * exps subtracts its maximum.  A row's sums over draws run in draw order and its sums over
+ * clusters in cluster order: no result depends on table_budget_bytes, bit for bit.
+ *
+ * hdpm_predict_build: the parameters of the M draws, total_cls[M] and sum_s K_s rows of d
+ *   centers and sigmas in saved-iteration order (what hdpm_record_take returns), kept on the
+ *   device as a byte and dhamming's (match, mismatch) pair per (s, k, j).
+ * hdpm_predict_new: ny rows codes[ny x d].  lpd[y] = log((1/M) sum_s exp(lse^s)) - log(N + gamma),
+ *   the log posterior predictive density; p_new[y] = (1/M) sum_s r^s_0, the probability of a
+ *   cluster of its own; with a partition cl[N] of the training points into classes 0..Ka-1
+ *   (1 <= Ka <= 255) and T^s its contingency table against draw s, coclass[y * Ka + a] =
+ *   (1 / (M n_a)) sum_s sum_{k >= 1} r^s_k T^s[a][k], the mean over the points i of class a of the
+ *   probability that y is clustered with i (0 for an empty class).  Any output may be NULL
+ *   and a call computes only what its outputs need: without coclass no table pass runs and cl
+ *   is not read.  Rows go through in blocks whose device staging obeys table_budget_bytes
+ *   (at least 64 rows per block).
+ * hdpm_predict_own: the training rows codes[N x d] themselves; with l_s the ll of row i under
+ *   its own cluster z_s(i) in draw s, lppd[i] = log((1/M) sum_s exp(l_s)), logcpo[i] =
+ *   -log((1/M) sum_s exp(-l_s)) and var[i] the sample variance of l_s over the draws (ddof 1;
+ *   0.0 when M = 1).  WAIC = -2 sum_i (lppd[i] - var[i]) and LPML = sum_i logcpo[i] are the
+ *   caller's sums.  Any output may be NULL.
+ * hdpm_predict_loglik (testing and inspection): one draw s; ll[ny x K_s] and resp[ny x
+ *   (K_s + 1)], slot 0 the new cluster.  Either output may be NULL.
+ * HDPM_E_ARG with a message (naming the draw, cluster, row or attribute) for: a call before
+ * hdpm_trace_build or hdpm_predict_build; total_cls[s] different from the trace's cluster count
+ * of draw s; d or an attrisize outside what hdpm_set_data accepts; a center that is not an
+ * integer in 1..m_j; a sigma that is not finite and > 0; gamma <= 0; a code outside 1..m_j;
+ * a cl label >= Ka, or Ka outside 1..255; s outside 0..M-1. */
+int hdpm_predict_build(hdpm_ctx* ctx, int32_t d, const int32_t* attrisize, double gamma, const int32_t* total_cls,
+                       const double* centers, const double* sigmas);
+int hdpm_predict_new(hdpm_ctx* ctx, const uint8_t* codes, int32_t ny, const int32_t* cl, int32_t Ka, double* lpd,
+                     double* p_new, double* coclass);
+int hdpm_predict_own(hdpm_ctx* ctx, const uint8_t* codes, double* lppd, double* var, double* logcpo);
+int hdpm_predict_loglik(hdpm_ctx* ctx, int32_t s, const uint8_t* codes, int32_t ny, double* ll, double* resp);
 /* Testing: one draw on the device from log-weights logw[E] (E <= 256) and the uniform rU --
  * the n8:95-102 categorical draw (two_way = 0; *pick = the 0-based index, or -status) or the
  * sm:204-215 two-way draw (two_way = 1, E = 2) -- with the engine's exp, glibc's algorithm

@@ -32,6 +32,7 @@ EXPORTS = (
     "hdpm_trace_build", "hdpm_trace_terms", "hdpm_trace_losses", "hdpm_trace_tables",
     "hdpm_trace_groups", "hdpm_trace_group_info", "hdpm_trace_avg_tree", "hdpm_trace_cut_losses",
     "hdpm_trace_cut_labels", "hdpm_trace_distances", "hdpm_trace_affinity", "hdpm_sm_last_terms",
+    "hdpm_predict_build", "hdpm_predict_new", "hdpm_predict_own", "hdpm_predict_loglik",
 )
 
 OPT_HIG_LOGSPACE = 1
@@ -217,6 +218,10 @@ def lib():
         "hdpm_trace_cut_labels": ([vp, i32, vp], C.c_int),
         "hdpm_trace_distances": ([vp, vp, i32, vp, vp, vp], C.c_int),
         "hdpm_trace_affinity": ([vp, vp, i32, vp, vp], C.c_int),
+        "hdpm_predict_build": ([vp, i32, vp, f64, vp, vp, vp], C.c_int),
+        "hdpm_predict_new": ([vp, vp, i32, vp, i32, vp, vp, vp], C.c_int),
+        "hdpm_predict_own": ([vp, vp, vp, vp, vp], C.c_int),
+        "hdpm_predict_loglik": ([vp, i32, vp, i32, vp, vp], C.c_int),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name)

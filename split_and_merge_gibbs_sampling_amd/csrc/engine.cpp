@@ -5533,6 +5533,24 @@ int hdpm_trace_cut_labels(hdpm_ctx* h, int32_t k, int32_t* cl) {
   CTX();
   GUARD(return ctx->sum.trace_cut_labels(k, cl);)
 }
+int hdpm_predict_build(hdpm_ctx* h, int32_t d, const int32_t* attrisize, double gamma, const int32_t* total_cls,
+                       const double* centers, const double* sigmas) {
+  CTX();
+  GUARD(return ctx->sum.predict_build(d, attrisize, gamma, total_cls, centers, sigmas);)
+}
+int hdpm_predict_new(hdpm_ctx* h, const uint8_t* codes, int32_t ny, const int32_t* cl, int32_t Ka, double* lpd,
+                     double* p_new, double* coclass) {
+  CTX();
+  GUARD(return ctx->sum.predict_new(codes, ny, cl, Ka, lpd, p_new, coclass);)
+}
+int hdpm_predict_own(hdpm_ctx* h, const uint8_t* codes, double* lppd, double* var, double* logcpo) {
+  CTX();
+  GUARD(return ctx->sum.predict_own(codes, lppd, var, logcpo);)
+}
+int hdpm_predict_loglik(hdpm_ctx* h, int32_t s, const uint8_t* codes, int32_t ny, double* ll, double* resp) {
+  CTX();
+  GUARD(return ctx->sum.predict_loglik(s, codes, ny, ll, resp);)
+}
 int hdpm_debug_draw(hdpm_ctx* h, const double* logw, int32_t E, double rU, int32_t two_way, int32_t ocml,
                     int32_t* pick) {
   CTX();

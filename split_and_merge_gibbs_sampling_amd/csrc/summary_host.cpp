@@ -1,7 +1,9 @@
 // summary_host.cpp -- host side of the posterior summaries (summary_host.hpp): the dense
 // psm of posterior.hip, the matrix-free summaries of trace_summary.hip, the uncertainty
-// calls of trace_uncertainty.hip and the average-linkage search of trace_tree.hpp.  The
-// arithmetic that turns the device's integer sums into losses is in trace_loss.hpp.
+// calls of trace_uncertainty.hip, the average-linkage search of trace_tree.hpp and the
+// posterior predictive of predict.hip.  The arithmetic that turns the device's integer sums
+// into losses is in trace_loss.hpp, that of the predictive's tables and checks in
+// predict_host.hpp.
 #include "summary_host.hpp"
 
 #include <algorithm>
@@ -10,6 +12,7 @@
 #include <utility>
 
 #include "../../include/hdpm.h"
+#include "predict_host.hpp"
 #include "summary_launch.hpp"
 #include "trace_loss.hpp"
 #include "trace_tree.hpp"
@@ -241,6 +244,7 @@ int Summaries::trace_build(const int32_t* c_trace, int32_t M, int32_t N, int64_t
   if (mx < 0) { err = "trace: labels must be in 0..254"; return HDPM_E_ARG; }
   tr_N = 0;   // no trace until this one is complete
   tg_U = 0;   // and no groups or tree of the previous one
+  pr_d = 0;   // nor its draws' parameters
   tg_counts = tg_tree = false;
   const int Np = (int)(((int64_t)N + 15) & ~(int64_t)15);
   d_tr_lab.ensure((size_t)M * Np);
@@ -533,6 +537,212 @@ int Summaries::trace_cut_labels(int32_t k, int32_t* cl) {
   HIPCHK(launch_tg_expand(d_tg_of.p, d_tg_cutw.p, N, d_tg_cl.p, stream));
   HIPCHK(hipMemcpyAsync(cl, d_tg_cl.p, (size_t)N * 4, hipMemcpyDeviceToHost, stream));
   HIPCHK(hipStreamSynchronize(stream));
+  return HDPM_OK;
+}
+
+// ---- the posterior predictive from the recorded centers and sigmas (predict.hip)
+int Summaries::predict_build(int32_t d, const int32_t* attrisize, double gamma, const int32_t* total_cls,
+                             const double* centers, const double* sigmas) {
+  if (int st = need(false, false)) return st;
+  pr_d = 0;
+  if (!total_cls || !centers || !sigmas) { err = "predict: bad arguments"; return HDPM_E_ARG; }
+  err = pr_check_model(d, attrisize, gamma);
+  if (!err.empty()) return HDPM_E_ARG;
+  const int M = tr_M;
+  std::vector<uint32_t> sizes((size_t)M * 256);
+  HIPCHK(hipMemcpyAsync(sizes.data(), d_tr_sizes.p, sizes.size() * 4, hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipStreamSynchronize(stream));
+  pr_off.assign((size_t)M + 1, 0);
+  int Kmax = 0;
+  for (int s = 0; s < M; ++s) {
+    err = pr_check_draw(s, total_cls[s], sizes.data() + (size_t)s * 256);
+    if (!err.empty()) return HDPM_E_ARG;
+    pr_off[s + 1] = pr_off[s] + total_cls[s];
+    Kmax = std::max(Kmax, total_cls[s]);
+  }
+  for (int s = 0; s < M; ++s) {
+    err = pr_check_params(s, total_cls[s], d, attrisize, centers + (size_t)pr_off[s] * d,
+                          sigmas + (size_t)pr_off[s] * d);
+    if (!err.empty()) return HDPM_E_ARG;
+  }
+  const int64_t rows = pr_off[M];
+  const size_t d4 = (size_t)pr_d4(d);
+  std::vector<uint8_t> cen((size_t)rows * d4);
+  std::vector<double> mm((size_t)rows * d * 2), lognk((size_t)rows);
+  parallel_for(rows, [&](int64_t r0, int64_t r1) {
+    pr_build_tables(r1 - r0, d, attrisize, centers + (size_t)r0 * d, sigmas + (size_t)r0 * d, cen.data() + r0 * d4,
+                    mm.data() + (size_t)r0 * d * 2);
+  });
+  for (int s = 0; s < M; ++s)
+    for (int k = 0; k < total_cls[s]; ++k) lognk[pr_off[s] + k] = std::log((double)sizes[(size_t)s * 256 + k]);
+  d_pr_cen.ensure(cen.size());
+  d_pr_mm.ensure(mm.size());
+  d_pr_lognk.ensure(lognk.size());
+  d_pr_off.ensure(pr_off.size());
+  HIPCHK(hipMemcpyAsync(d_pr_cen.p, cen.data(), cen.size(), hipMemcpyHostToDevice, stream));
+  HIPCHK(hipMemcpyAsync(d_pr_mm.p, mm.data(), mm.size() * 8, hipMemcpyHostToDevice, stream));
+  HIPCHK(hipMemcpyAsync(d_pr_lognk.p, lognk.data(), lognk.size() * 8, hipMemcpyHostToDevice, stream));
+  HIPCHK(hipMemcpyAsync(d_pr_off.p, pr_off.data(), pr_off.size() * 8, hipMemcpyHostToDevice, stream));
+  HIPCHK(hipStreamSynchronize(stream));
+  pr_att.assign(attrisize, attrisize + d);
+  pr_gamma = gamma;
+  pr_w0 = std::log(gamma) + pr_ll0(d, attrisize);
+  pr_Kmax = Kmax;
+  pr_d = d;
+  return HDPM_OK;
+}
+
+// what every predict call needs: a trace, its parameters, and rows of codes in range
+int Summaries::need_predict(const uint8_t* codes, int64_t rows) {
+  if (int st = need(false, false)) return st;
+  if (pr_d == 0) { err = "predict: hdpm_predict_build has not been called"; return HDPM_E_ARG; }
+  if (!codes || rows <= 0) { err = "predict: no rows"; return HDPM_E_ARG; }
+  std::atomic<int64_t> bad{-1};
+  parallel_for(rows, [&](int64_t r0, int64_t r1) {
+    const int64_t at = pr_bad_code(codes + (size_t)r0 * pr_d, r1 - r0, pr_d, pr_att.data());
+    if (at < 0) return;
+    int64_t seen = bad.load(), mine = r0 * pr_d + at;
+    while ((seen < 0 || mine < seen) && !bad.compare_exchange_weak(seen, mine)) {}
+  });
+  if (bad.load() >= 0) { err = pr_code_message(bad.load(), pr_d); return HDPM_E_ARG; }
+  return HDPM_OK;
+}
+
+// Rows in blocks whose device staging (packed codes, scratch columns, outputs) obeys the table
+// budget, against draws s0 .. s1 - 1; each block's results go to the caller as it completes.
+// tab: the tables of the partition (Ka classes) for coclass.  ll / resp: one draw.  A row's
+// results do not depend on the block it falls in.
+void Summaries::predict_blocks(const uint8_t* codes, int64_t ny, int s0, int s1, const uint32_t* tab, int Ka,
+                               double* lpd, double* p_new, double* coclass, double* ll, double* resp) {
+  const int d = pr_d;
+  const size_t nw = (size_t)pr_d4(d) / 4;
+  const size_t K1 = (size_t)(pr_off[s0 + 1] - pr_off[s0]);   // the clusters of the one draw of ll / resp
+  const size_t per_row = nw * 4 + ((size_t)pr_Kmax + 1) * 8 + (tab ? (size_t)Ka * 8 : 0) + 16 + (ll ? K1 * 8 : 0) +
+                         (resp ? (K1 + 1) * 8 : 0);
+  const size_t nb = pr_block(tr_budget, per_row, (size_t)ny);
+  d_pr_cw.ensure(nw * nb);
+  d_pr_w.ensure(((size_t)pr_Kmax + 1) * nb);
+  d_pr_out.ensure(2 * nb);
+  if (tab) d_pr_cc.ensure((size_t)Ka * nb);
+  if (ll) d_pr_ll.ensure(K1 * nb);
+  if (resp) d_pr_resp.ensure((K1 + 1) * nb);
+  std::vector<uint32_t> cw(nw * nb);
+  std::vector<double> t;
+  auto take = [&](const double* dev, size_t cols, int64_t i0, int64_t nr, double* out) {
+    // cols x nb on the device to rows of cols values
+    t.resize(cols * nb);
+    HIPCHK(hipMemcpyAsync(t.data(), dev, t.size() * 8, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    parallel_for(nr, [&](int64_t r0, int64_t r1) {
+      for (int64_t r = r0; r < r1; ++r)
+        for (size_t c = 0; c < cols; ++c) out[(size_t)(i0 + r) * cols + c] = t[c * nb + r];
+    });
+  };
+  for (int64_t i0 = 0; i0 < ny; i0 += (int64_t)nb) {
+    const int64_t nr = std::min<int64_t>((int64_t)nb, ny - i0);
+    parallel_for(nr, [&](int64_t r0, int64_t r1) { pr_pack_rows(codes + (size_t)i0 * d, r0, r1, d, nb, cw.data()); });
+    HIPCHK(hipMemcpyAsync(d_pr_cw.p, cw.data(), cw.size() * 4, hipMemcpyHostToDevice, stream));
+    PrNewArgs a{};
+    a.cw = d_pr_cw.p;
+    a.nrows = nr;
+    a.nbp = (int64_t)nb;
+    a.d = d;
+    a.s0 = s0;
+    a.s1 = s1;
+    a.cen = d_pr_cen.p;
+    a.mm = d_pr_mm.p;
+    a.lognk = d_pr_lognk.p;
+    a.off = d_pr_off.p;
+    a.w0 = pr_w0;
+    a.log_ng = std::log((double)tr_N + pr_gamma);
+    a.w = d_pr_w.p;
+    a.tab = tab;
+    a.Ka = Ka;
+    a.Kz = tr_Kz;
+    a.na = d_pr_na.p;
+    a.cc = d_pr_cc.p;
+    a.lpd = lpd ? d_pr_out.p : nullptr;
+    a.p_new = p_new ? d_pr_out.p + nb : nullptr;
+    a.ll_out = ll ? d_pr_ll.p : nullptr;
+    a.resp_out = resp ? d_pr_resp.p : nullptr;
+    HIPCHK(launch_pr_new(a, stream));
+    if (lpd) HIPCHK(hipMemcpyAsync(lpd + i0, d_pr_out.p, (size_t)nr * 8, hipMemcpyDeviceToHost, stream));
+    if (p_new) HIPCHK(hipMemcpyAsync(p_new + i0, d_pr_out.p + nb, (size_t)nr * 8, hipMemcpyDeviceToHost, stream));
+    if (tab) take(d_pr_cc.p, (size_t)Ka, i0, nr, coclass);
+    if (ll) take(d_pr_ll.p, K1, i0, nr, ll);
+    if (resp) take(d_pr_resp.p, K1 + 1, i0, nr, resp);
+    HIPCHK(hipStreamSynchronize(stream));
+  }
+}
+
+int Summaries::predict_new(const uint8_t* codes, int32_t ny, const int32_t* cl, int32_t Ka, double* lpd,
+                           double* p_new, double* coclass) {
+  if (int st = need_predict(codes, ny)) return st;
+  if (coclass) {
+    if (!cl) { err = "predict: coclass needs a partition of the training points"; return HDPM_E_ARG; }
+    err = pr_check_classes(cl, tr_N, Ka);
+    if (!err.empty()) return HDPM_E_ARG;
+  }
+  if (!lpd && !p_new && !coclass) return HDPM_OK;
+  if (!coclass) {
+    predict_blocks(codes, ny, 0, tr_M, nullptr, 0, lpd, p_new, nullptr, nullptr, nullptr);
+    return HDPM_OK;
+  }
+  std::vector<double> na((size_t)Ka, 0.0);
+  for (int i = 0; i < tr_N; ++i) na[cl[i]] += 1.0;
+  d_pr_na.ensure((size_t)Ka);
+  HIPCHK(hipMemcpyAsync(d_pr_na.p, na.data(), (size_t)Ka * 8, hipMemcpyHostToDevice, stream));
+  // one candidate always fits a block: its tables stay on the device while the rows go through
+  blocks({cl, 0, 1}, Ka, false, false, false, [&](int, int, const uint8_t*) {
+    predict_blocks(codes, ny, 0, tr_M, d_tr_tab.p, Ka, lpd, p_new, coclass, nullptr, nullptr);
+  });
+  return HDPM_OK;
+}
+
+int Summaries::predict_own(const uint8_t* codes, double* lppd, double* var, double* logcpo) {
+  if (int st = need_predict(codes, tr_N)) return st;
+  if (!lppd && !var && !logcpo) return HDPM_OK;
+  const int d = pr_d, N = tr_N;
+  const size_t nw = (size_t)pr_d4(d) / 4;
+  const size_t nb = pr_block(tr_budget, nw * 4 + 24, (size_t)N);
+  d_pr_cw.ensure(nw * nb);
+  d_pr_out.ensure(3 * nb);
+  std::vector<uint32_t> cw(nw * nb);
+  for (int64_t i0 = 0; i0 < N; i0 += (int64_t)nb) {
+    const int64_t nr = std::min<int64_t>((int64_t)nb, N - i0);
+    parallel_for(nr, [&](int64_t r0, int64_t r1) { pr_pack_rows(codes + (size_t)i0 * d, r0, r1, d, nb, cw.data()); });
+    HIPCHK(hipMemcpyAsync(d_pr_cw.p, cw.data(), cw.size() * 4, hipMemcpyHostToDevice, stream));
+    PrOwnArgs a{};
+    a.cw = d_pr_cw.p;
+    a.nrows = nr;
+    a.nbp = (int64_t)nb;
+    a.row0 = i0;
+    a.d = d;
+    a.M = tr_M;
+    a.Np = tr_Np;
+    a.lab = d_tr_lab.p;
+    a.cen = d_pr_cen.p;
+    a.mm = d_pr_mm.p;
+    a.off = d_pr_off.p;
+    a.lppd = lppd ? d_pr_out.p : nullptr;
+    a.var = var ? d_pr_out.p + nb : nullptr;
+    a.logcpo = logcpo ? d_pr_out.p + 2 * nb : nullptr;
+    HIPCHK(launch_pr_own(a, stream));
+    if (lppd) HIPCHK(hipMemcpyAsync(lppd + i0, d_pr_out.p, (size_t)nr * 8, hipMemcpyDeviceToHost, stream));
+    if (var) HIPCHK(hipMemcpyAsync(var + i0, d_pr_out.p + nb, (size_t)nr * 8, hipMemcpyDeviceToHost, stream));
+    if (logcpo) HIPCHK(hipMemcpyAsync(logcpo + i0, d_pr_out.p + 2 * nb, (size_t)nr * 8, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+  }
+  return HDPM_OK;
+}
+
+int Summaries::predict_loglik(int32_t s, const uint8_t* codes, int32_t ny, double* ll, double* resp) {
+  if (int st = need_predict(codes, ny)) return st;
+  if (s < 0 || s >= tr_M) {
+    err = "predict: draw " + std::to_string(s) + " is outside 0.." + std::to_string(tr_M - 1);
+    return HDPM_E_ARG;
+  }
+  if (ll || resp) predict_blocks(codes, ny, s, s + 1, nullptr, 0, nullptr, nullptr, nullptr, ll, resp);
   return HDPM_OK;
 }
 

@@ -1,5 +1,6 @@
 // summary_host.hpp -- the posterior summaries of a context: the state and host logic behind
-// hdpm_psm_* (posterior.hip) and hdpm_trace_* (trace_summary.hip, trace_uncertainty.hip).
+// hdpm_psm_* (posterior.hip), hdpm_trace_* (trace_summary.hip, trace_uncertainty.hip) and
+// hdpm_predict_* (predict.hip).
 //
 // The summaries work on saved labels and never touch chain state: of their context they use
 // the main stream and the error string, bound at construction.  Every method is the body of
@@ -34,6 +35,13 @@ class Summaries {
   int trace_avg_tree(int32_t* merge, double* height);
   int trace_cut_losses(int32_t k0, int32_t nk, double* vi_lb, double* vi, uint64_t* binder_A, uint64_t* binder_Q);
   int trace_cut_labels(int32_t k, int32_t* cl);
+
+  int predict_build(int32_t d, const int32_t* attrisize, double gamma, const int32_t* total_cls,
+                    const double* centers, const double* sigmas);
+  int predict_new(const uint8_t* codes, int32_t ny, const int32_t* cl, int32_t Ka, double* lpd, double* p_new,
+                  double* coclass);
+  int predict_own(const uint8_t* codes, double* lppd, double* var, double* logcpo);
+  int predict_loglik(int32_t s, const uint8_t* codes, int32_t ny, double* ll, double* resp);
 
  private:
   hipStream_t& stream;
@@ -76,7 +84,22 @@ class Summaries {
   std::vector<int32_t> tg_merge;
   std::vector<double> tg_height;
 
+  // hdpm_predict_*: the parameter tables of the trace's draws (parameter row pr_off[s] + k is
+  // cluster k of draw s: center bytes, (match, mismatch) pairs, log sizes) and, per block of
+  // rows, the packed codes, the scratch columns and the outputs
+  DevBuf<uint8_t> d_pr_cen;
+  DevBuf<double> d_pr_mm, d_pr_lognk, d_pr_w, d_pr_cc, d_pr_na, d_pr_out, d_pr_ll, d_pr_resp;
+  DevBuf<int64_t> d_pr_off;
+  DevBuf<uint32_t> d_pr_cw;
+  std::vector<int64_t> pr_off;
+  std::vector<int32_t> pr_att;
+  int pr_d = 0, pr_Kmax = 0;   // pr_d == 0: no parameters
+  double pr_gamma = 0.0, pr_w0 = 0.0;
+
   struct Cands;
+  int need_predict(const uint8_t* codes, int64_t rows);
+  void predict_blocks(const uint8_t* codes, int64_t ny, int s0, int s1, const uint32_t* tab, int Ka, double* lpd,
+                      double* p_new, double* coclass, double* ll, double* resp);
   int need(bool groups, bool tree);
   int check(const int32_t* cls, int ncand, int* Ka);
   template <class F>

@@ -1,8 +1,8 @@
 // summary_launch.hpp -- launchers of the posterior-summary kernels: posterior.hip
 // (launch_psm, launch_vi_terms), trace_summary.hip (launch_tr_pack .. launch_tr_reduce,
 // launch_tg_*) and trace_uncertainty.hip (launch_tr_transpose, launch_tr_affinity,
-// launch_tr_cross).  Included by the units that define them and by summary_host.cpp, their
-// only caller.
+// launch_tr_cross) and predict.hip (launch_pr_new, launch_pr_own).  Included by the units that
+// define them and by summary_host.cpp, their only caller.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -38,5 +38,48 @@ hipError_t launch_tg_tables(const uint8_t* sigT, const uint8_t* cut, const uint3
 hipError_t launch_tg_gather(const uint8_t* sigT, const uint8_t* cut, int U, int Up, int M, int ncut, int Ka, int Kz,
                             const uint32_t* tab, const uint32_t* sizes, uint64_t* all, uint64_t* same, hipStream_t s);
 hipError_t launch_tg_expand(const uint32_t* group_of, const int32_t* cut, int N, int32_t* cl, hipStream_t s);
+
+// predict.hip.  The parameter tables of all draws (predict_host.hpp): parameter row off[s] + k
+// is cluster k of draw s; cen holds its centers as bytes (rows of d rounded up to a multiple
+// of 4), mm its (match, mismatch) pairs (rows of d pairs), lognk its log size.  A block of
+// rows is cw: word w of row r, four codes, at cw[w * nbp + r].
+constexpr int kPrThreads = 256;     // rows of a tile, one per lane
+constexpr int kPrG = 8;             // clusters staged together = accumulators of a lane
+constexpr int kPrDC = 256;          // attributes of a staged chunk (a multiple of 4)
+constexpr int kPrOwnDraws = 4;      // draws in flight per lane of k_pr_own
+
+struct PrNewArgs {
+  const uint32_t* cw;
+  int64_t nrows, nbp;
+  int d, s0, s1;                    // draws s0 .. s1 - 1
+  const uint8_t* cen;
+  const double* mm;
+  const double* lognk;
+  const int64_t* off;               // M + 1
+  double w0, log_ng;                // log gamma + ll_0; log(N + gamma)
+  double* w;                        // scratch, (Kmax + 1) x nbp
+  const uint32_t* tab;              // T^s[a][k] as k_tr_tables lays it out (M x Ka x Kz), or null
+  int Ka, Kz;
+  const double* na;                 // Ka class sizes
+  double* cc;                       // Ka x nbp: the fold's running sums, coclass at the end
+  double* lpd;                      // nbp each, or null
+  double* p_new;
+  double* ll_out;                   // one draw: K x nbp, or null
+  double* resp_out;                 // one draw: (K + 1) x nbp, slot 0 the new cluster, or null
+};
+struct PrOwnArgs {
+  const uint32_t* cw;
+  int64_t nrows, nbp, row0;         // the block's first row is point row0 of the trace
+  int d, M, Np;
+  const uint8_t* lab;               // the trace's label bytes, M x Np
+  const uint8_t* cen;
+  const double* mm;
+  const int64_t* off;
+  double* lppd;                     // nbp each, or null
+  double* var;
+  double* logcpo;
+};
+hipError_t launch_pr_new(const PrNewArgs& a, hipStream_t s);
+hipError_t launch_pr_own(const PrOwnArgs& a, hipStream_t s);
 
 }  // namespace hdpm

@@ -18,7 +18,11 @@ default search -- the cuts of the average-linkage tree -- on the groups of point
 labels agree in every draw, again with no matrix.  ``credible_ball`` (mcclust.ext
 ``credibleball``) and ``LabelTrace.membership`` / ``cluster_similarity`` (the content of the
 script's PSM plot ordered by ``VI$cl``) say how far that estimate can be trusted, from the
-same tables (csrc/trace_uncertainty.hip).  ``arandi``, ``ess`` and ``iat`` are
+same tables (csrc/trace_uncertainty.hip).  ``Predictive`` reads the recorded centers and
+sigmas beside the labels (csrc/predict.hip through ``hdpm_predict_*``): the posterior
+predictive of rows the chain never saw -- their density, their class of a point estimate, the
+probability of a cluster of their own -- and the pointwise log-likelihood of the training rows
+behind ``waic`` and ``lpml``.  ``arandi``, ``ess`` and ``iat`` are
 restated on the host.  None of these packages is installed here (no R), so their parity is
 unpinned; ``arandi`` is checked against scikit-learn's adjusted Rand score.
 """
@@ -123,6 +127,7 @@ class LabelTrace:
         if tr.ndim != 2 or tr.size == 0:
             raise ValueError("c_trace must be M x N")
         self.M, self.N = tr.shape
+        self._lo, self._hi = tr.min(axis=1), tr.max(axis=1)     # the saved labels' range per draw (Predictive)
         tr = np.ascontiguousarray(_relabel(tr, "iteration"))
         self._own = engine is None
         self.eng = Engine(device) if engine is None else engine
@@ -311,6 +316,119 @@ class LabelTrace:
         self.eng._check(self.eng._L.hdpm_trace_cut_losses(self.eng._h, int(k0), int(nk), ptr(lb), ptr(v), ptr(a),
                                                           ptr(q)))
         return lb, v, a, q
+
+
+class Predictive:
+    """The posterior predictive from the recorded draws (csrc/predict.hip through
+    ``hdpm_predict_*``; the model and the orders of summation are in include/hdpm.h).
+
+    ``trace`` is the ``LabelTrace`` of the saved labels; ``centers`` and ``sigmas`` are the
+    lists of K_s x d arrays that ``run_markov_chain(..., keep_params=True)`` returns for the
+    same saved iterations; ``attrisize`` and ``gamma`` are the chain's.  Label k of draw s
+    names row k of that draw's parameters, so the saved labels of draw s must be exactly
+    0..K_s-1 (ValueError otherwise): ``LabelTrace``'s relabelling is then the identity.  Rows
+    hold codes 1..m_j.  The trace's ``table_budget`` bounds the device staging of a block of
+    rows and changes no result."""
+
+    def __init__(self, trace: LabelTrace, centers, sigmas, attrisize, gamma: float):
+        if not isinstance(trace, LabelTrace):
+            raise ValueError("Predictive needs a LabelTrace")
+        if len(centers) != trace.M or len(sigmas) != trace.M:
+            raise ValueError("centers and sigmas must hold one array per saved iteration")
+        self.trace, self.M, self.N = trace, trace.M, trace.N
+        self.att = np.ascontiguousarray(attrisize, dtype=np.int32).ravel()
+        self.d = int(self.att.size)
+        cen = [np.asarray(c, np.float64).reshape(-1, self.d) for c in centers]
+        sig = [np.asarray(s, np.float64).reshape(-1, self.d) for s in sigmas]
+        self.K = np.array([c.shape[0] for c in cen], np.int32)
+        eng = trace.eng
+        # K_s distinct labels with smallest 0 and largest K_s - 1 are exactly 0..K_s-1
+        draw_k, one = np.zeros(self.M, np.int32), np.zeros((1, self.N), np.int32)
+        eng._check(eng._L.hdpm_trace_distances(eng._h, ptr(one), 1, None, None, ptr(draw_k)))
+        for s in range(self.M):
+            if sig[s].shape != cen[s].shape:
+                raise ValueError(f"draw {s}: centers and sigmas differ in shape")
+            if trace._lo[s] != 0 or trace._hi[s] != self.K[s] - 1 or draw_k[s] != self.K[s]:
+                raise ValueError(f"draw {s}: the saved labels must be exactly 0..{self.K[s] - 1}")
+        cen_all, sig_all = np.ascontiguousarray(np.concatenate(cen)), np.ascontiguousarray(np.concatenate(sig))
+        eng._check(eng._L.hdpm_predict_build(eng._h, self.d, ptr(self.att), float(gamma), ptr(self.K), ptr(cen_all),
+                                             ptr(sig_all)))
+
+    def _rows(self, Y) -> np.ndarray:
+        y = np.asarray(Y)
+        if y.ndim != 2 or y.shape[1] != self.d or y.shape[0] == 0:
+            raise ValueError("rows must be ny x d")
+        if y.min() < 0 or y.max() > 255:
+            raise ValueError("codes must lie in 1..attrisize[j]")
+        return np.ascontiguousarray(y, dtype=np.uint8)
+
+    def density(self, Y) -> np.ndarray:
+        """lpd[y]: the log posterior predictive density of each row of ``Y``."""
+        return self._new(Y, None, True, False)[0]
+
+    def _new(self, Y, cl, want_lpd, want_pnew, Ka=None):
+        y = self._rows(Y)
+        eng = self.trace.eng
+        lpd = np.zeros(y.shape[0]) if want_lpd else None
+        pn = np.zeros(y.shape[0]) if want_pnew else None
+        co, c = None, None
+        if cl is not None and Ka is not None:
+            c = np.ascontiguousarray(cl, dtype=np.int32).ravel()
+            if c.size != self.N:
+                raise ValueError("the partition must have N labels")
+        elif cl is not None:
+            c = self.trace._one(cl)[0]
+            Ka = int(c.max()) + 1
+        if cl is not None:
+            co = np.zeros((y.shape[0], max(int(Ka), 0)))
+        eng._check(eng._L.hdpm_predict_new(eng._h, ptr(y), y.shape[0], ptr(c), int(Ka or 0), ptr(lpd), ptr(pn),
+                                           ptr(co)))
+        return lpd, pn, co
+
+    def classify(self, Y, cl, Ka: int | None = None):
+        """(class, coclass, p_new) of each row of ``Y`` against the partition ``cl`` of the
+        training points (relabelled 0..Ka-1 in order of the labels' values, as the trace's
+        candidates are; with ``Ka`` given, taken as labels 0..Ka-1 as they stand, so a class
+        may be empty: its column is 0): coclass[y][a] is the mean over the points i of class a of the
+        posterior probability that y is clustered with i, class its arg-max, and p_new[y] the
+        posterior probability that y opens a cluster of its own."""
+        _, pn, co = self._new(Y, cl, False, True, Ka)
+        return np.argmax(co, axis=1), co, pn
+
+    def pointwise(self, X):
+        """(lppd, var, logcpo) of the N training rows ``X`` (the rows the chain ran on): per
+        row the log mean likelihood under its own cluster over the draws, the sample variance
+        of that log-likelihood, and the log conditional predictive ordinate."""
+        x = self._rows(X)
+        if x.shape[0] != self.N:
+            raise ValueError("pointwise needs the N training rows")
+        eng = self.trace.eng
+        lppd, var, cpo = np.zeros(self.N), np.zeros(self.N), np.zeros(self.N)
+        eng._check(eng._L.hdpm_predict_own(eng._h, ptr(x), ptr(lppd), ptr(var), ptr(cpo)))
+        return lppd, var, cpo
+
+    def loglik(self, s: int, Y):
+        """(ll, resp) of draw ``s`` alone: ll[y][k] the log-density of row y under cluster k
+        (ny x K_s) and resp[y] the urn's probabilities, slot 0 the new cluster (ny x (K_s + 1));
+        testing and inspection."""
+        y = self._rows(Y)
+        eng = self.trace.eng
+        K = int(self.K[s]) if 0 <= int(s) < self.M else 1
+        ll, resp = np.zeros((y.shape[0], K)), np.zeros((y.shape[0], K + 1))
+        eng._check(eng._L.hdpm_predict_loglik(eng._h, int(s), ptr(y), y.shape[0], ptr(ll), ptr(resp)))
+        return ll, resp
+
+
+def waic(pointwise) -> float:
+    """WAIC = -2 sum_i (lppd[i] - var[i]) of ``Predictive.pointwise``'s result, the sum exact
+    (``math.fsum``)."""
+    lppd, var, _ = pointwise
+    return -2.0 * math.fsum(float(a) - float(b) for a, b in zip(lppd, var))
+
+
+def lpml(pointwise) -> float:
+    """LPML = sum_i logcpo[i] of ``Predictive.pointwise``'s result (``math.fsum``)."""
+    return math.fsum(float(x) for x in pointwise[2])
 
 
 def _avg_cuts(trace, max_k, max_groups):
