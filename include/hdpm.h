@@ -609,6 +609,33 @@ int hdpm_debug_draw(hdpm_ctx* ctx, const double* logw, int32_t E, double rU, int
 /* Testing: exp (fn = 0) or log (fn = 1) of x[n] on the device, glibc's algorithm (ocml = 0)
  * or the device libm's (ocml = 1). */
 int hdpm_debug_math(hdpm_ctx* ctx, const double* x, int64_t n, int32_t fn, int32_t ocml, double* out);
+/* Testing: what the last launches of this process actually used, from the host's own
+ * bookkeeping (no kernel, nothing queued or waited for, a prepared sweep stays prepared).  The
+ * HDPM_* environment switches (csrc/switches.hpp) override launch geometry and select paths,
+ * and one outside its range, or a group size that does not fit, falls back silently: a test of
+ * a switch reads here that its path ran.  -1: no such launch yet.
+ *   phi_*: the fast device update_phi (launch_phi2): its group size, groups per cluster, the
+ *     threads of k_phi2_group and k_phi2_tree, the waves of k_phi2_values; phi_gs_refused: 1 when
+ *     the last plan under HDPM_PHI2_GS found that size not to fit (no fast path then), 0 when
+ *     it took it.
+ *   wide_*: k_prepass_wide's grid, chunks (16 points each) and claim flag; wide_launches counts
+ *     its launches.
+ *   mt_*: the stream generator's last window: the workgroups and blocks per workgroup of the
+ *     jump tables it holds (0: none built), whether the window ran on them (mt_multi) and its
+ *     draws (mt_window, saturating); mt_multi_windows counts the windows that did.
+ *   dense_direct, lbound, spec_lv: the last sweep launch's prepass arguments of these names.
+ *   mass_static: k_exact_rows_mass's fixed-order flag at its last launch.
+ *   dense_direct_launches, lbound_launches: the sweep launches so far with that argument set;
+ *     unsettled_margin_launches: those that listed by margins alone behind an unsettled launch
+ *     (what HDPM_FP_UNSETTLED_UNIF=0 asks for). */
+typedef struct hdpm_launches {
+  int32_t phi_gs, phi_G, phi_group_threads, phi_tree_threads, phi_values_waves, phi_gs_refused;
+  int32_t wide_grid, wide_chunks, wide_claim, wide_launches;
+  int32_t mt_G, mt_bpg, mt_multi, mt_window, mt_multi_windows;
+  int32_t dense_direct, lbound, spec_lv, mass_static;
+  int32_t dense_direct_launches, lbound_launches, unsettled_margin_launches;
+} hdpm_launches;
+int hdpm_debug_launches(hdpm_ctx* ctx, hdpm_launches* out);
 /* Block until every kernel and copy the context has queued is done, a prepared next
  * sweep's prefix (scratch outputs only) included; the prepared sweep stays prepared. */
 int hdpm_synchronize(hdpm_ctx* ctx);

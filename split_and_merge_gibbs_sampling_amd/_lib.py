@@ -33,6 +33,7 @@ EXPORTS = (
     "hdpm_trace_groups", "hdpm_trace_group_info", "hdpm_trace_avg_tree", "hdpm_trace_cut_losses",
     "hdpm_trace_cut_labels", "hdpm_trace_distances", "hdpm_trace_affinity", "hdpm_sm_last_terms",
     "hdpm_predict_build", "hdpm_predict_new", "hdpm_predict_own", "hdpm_predict_loglik",
+    "hdpm_debug_launches",
 )
 
 OPT_HIG_LOGSPACE = 1
@@ -143,6 +144,19 @@ class SmTerms(C.Structure):
                 "log_ratio": self.log_ratio, "log_u": self.log_u}
 
 
+class Launches(C.Structure):
+    """hdpm_launches (include/hdpm.h): what the process's last launches used."""
+    _fields_ = [(n, C.c_int32) for n in (
+        "phi_gs", "phi_G", "phi_group_threads", "phi_tree_threads", "phi_values_waves", "phi_gs_refused",
+        "wide_grid", "wide_chunks", "wide_claim", "wide_launches",
+        "mt_G", "mt_bpg", "mt_multi", "mt_window", "mt_multi_windows",
+        "dense_direct", "lbound", "spec_lv", "mass_static",
+        "dense_direct_launches", "lbound_launches", "unsettled_margin_launches")]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 def build(force: bool = False) -> str:
     """Compile the HIP kernels + host runtime for gfx950 into LIB_PATH (hipcc)."""
     srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC)]
@@ -204,6 +218,7 @@ def lib():
         "hdpm_get_option": ([vp, i32, P(f64)], C.c_int),
         "hdpm_debug_draw": ([vp, vp, i32, f64, i32, i32, P(i32)], C.c_int),
         "hdpm_debug_math": ([vp, vp, i64, i32, i32, vp], C.c_int),
+        "hdpm_debug_launches": ([vp, P(Launches)], C.c_int),
         "hdpm_psm_build": ([vp, vp, i32, i32], C.c_int),
         "hdpm_psm_rows": ([vp, i32, i32, vp], C.c_int),
         "hdpm_psm_vi_lb": ([vp, vp, i32, vp], C.c_int),

@@ -1064,6 +1064,11 @@ struct Ctx {
     const bool multi = mt_G > 1 && W.count >= (int64_t)mt_G * 624 * 8;
     MtGenArgs a{W.init_src ? W.init_src : W.init.p, W.mti0, W.count, W.raw.p, W.arrays.p, W.nblocks, W.export_from,
                 multi ? d_jpoly.p : nullptr, d_jidx.p, d_joff.p, mt_bpg, multi ? mt_G : 1};
+    launch_note(kLfMtG, mt_G);
+    launch_note(kLfMtBpg, mt_bpg);
+    launch_note(kLfMtMulti, multi);
+    launch_note(kLfMtWindow, (int32_t)std::min<int64_t>(W.count, INT32_MAX));
+    if (multi) launch_tick(kLfMtMultiWindows);
     HIPCHK(launch_mt_gen(a, gstream));
     HIPCHK(hipEventRecord(W.done, gstream));
     W.gen++;
@@ -2249,6 +2254,14 @@ struct Ctx {
     pa.exact_pref = exact_pref;
     // a dense launch needs no bounds: its list is every point (k_dense_list)
     pa.dense_direct = dense_list && sw::get<sw::DENSE_DIRECT>() ? 1 : 0;
+    if (part != kRoundResolve) {
+      launch_note(kLfDenseDirect, pa.dense_direct);
+      launch_note(kLfLbound, pa.lbound);
+      launch_note(kLfSpecLv, pa.spec_lv);
+      if (pa.dense_direct) launch_tick(kLfDenseDirectLaunches);
+      if (pa.lbound) launch_tick(kLfLboundLaunches);
+      if (unsettled_margins) launch_tick(kLfUnsettledMarginLaunches);
+    }
     pa.spec = ((debug & HDPM_DBG_NO_SNAPSHOT) || (el >= kMassNoSpec && !pa.spec_lv)) ? nullptr : d_spec.p;
     pa.spec_rad = d_spec_rad.p;
     pa.rq = d_rq.p;
@@ -3923,6 +3936,7 @@ struct Ctx {
       int pick = 0;
       if (gs_force) {
         if (fits(gs_force)) pick = gs_force;
+        launch_note(kLfPhiGsRefused, pick == 0);
       } else {
         for (int gs = 64; gs >= 8 && !pick; gs /= 2)
           if (fits(gs) && (int64_t)T * ((d + gs - 1) / gs) >= 160) pick = gs;
@@ -5581,6 +5595,14 @@ int hdpm_debug_math(hdpm_ctx* h, const double* x, int64_t n, int32_t fn, int32_t
     HIPCHK(hipStreamSynchronize(ctx->stream));
     return HDPM_OK;
   })
+}
+int hdpm_debug_launches(hdpm_ctx* h, hdpm_launches* out) {
+  // (read-only: a prepared sweep stays prepared, nothing is queued or waited for)
+  if (!h || !out) return HDPM_E_ARG;
+  static_assert(sizeof(hdpm_launches) == hdpm::kLaunchFields * sizeof(int32_t), "hdpm_launches is LaunchField's order");
+  int32_t* o = reinterpret_cast<int32_t*>(out);
+  for (int f = 0; f < hdpm::kLaunchFields; ++f) o[f] = hdpm::g_launch_log.v[f].load(std::memory_order_relaxed);
+  return HDPM_OK;
 }
 int hdpm_drop_prepared(hdpm_ctx* h) {
   CTX();

@@ -3558,6 +3558,10 @@ static hipError_t launch_prepass_w(const PrepassArgs& a, int nblocks, hipStream_
       // (the same number of chunks for every workgroup -- 875 workgroups x 5 chunks at C4 instead of
       // 1,024 x 4-5 -- measured 54 against 47 us: the kernel wants every resident wave)
       const int grid = std::min(nchunks, wide_grid(kern, lds, a.wide_per_cu));
+      launch_note(kLfWideGrid, grid);
+      launch_note(kLfWideChunks, nchunks);
+      launch_note(kLfWideClaim, sw::get<sw::WIDE_CLAIM>() != 0);
+      launch_tick(kLfWideLaunches);
       HDPM_LAUNCH(kern, dim3(grid), dim3(kWideThreads), lds, s, a, nchunks, sw::get<sw::WIDE_CLAIM>());
       return hipGetLastError();
     };
@@ -4133,6 +4137,7 @@ hipError_t launch_exact_rows(const PrepassArgs& a0, int nblocks, hipStream_t s, 
   if (a.exact_scan && !a.exact_wave && E <= kWave && mlds <= 96 * 1024) {
     HDPM_LAUNCH(k_exact_rows_mass, dim3(mass_grid(mlds)), dim3(kWave * kMassWaves), mlds, s, a,
                 sw::get<sw::MASS_STATIC>());
+    launch_note(kLfMassStatic, sw::get<sw::MASS_STATIC>() != 0);
     if (path) *path = 1;
     return hipGetLastError();
   }

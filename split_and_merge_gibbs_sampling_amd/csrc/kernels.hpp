@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <cstdint>
 
 #include <cstdio>
@@ -25,6 +26,31 @@ inline void sync_report(const char* name, hipStream_t s) {
     hipLaunchKernelGGL(kern, grid, block, lds, strm, __VA_ARGS__);          \
     if (::hdpm::sync_each()) ::hdpm::sync_report(#kern, strm);              \
   } while (0)
+
+// What this process's last launches actually used (hdpm_debug_launches, include/hdpm.h: the
+// fields of hdpm_launches in order): written by the host code that launches, read by the tests
+// of the HDPM_* switches -- an override outside its range, or one that does not fit, falls
+// back silently.  -1: no such launch yet; the *_launches / *_windows fields count from 0.
+enum LaunchField {
+  kLfPhiGs, kLfPhiG, kLfPhiGroupThreads, kLfPhiTreeThreads, kLfPhiValuesWaves, kLfPhiGsRefused,
+  kLfWideGrid, kLfWideChunks, kLfWideClaim, kLfWideLaunches,
+  kLfMtG, kLfMtBpg, kLfMtMulti, kLfMtWindow, kLfMtMultiWindows,
+  kLfDenseDirect, kLfLbound, kLfSpecLv, kLfMassStatic,
+  kLfDenseDirectLaunches, kLfLboundLaunches, kLfUnsettledMarginLaunches,
+  kLaunchFields
+};
+constexpr LaunchField kLaunchCounters[] = {kLfWideLaunches, kLfMtMultiWindows, kLfDenseDirectLaunches, kLfLboundLaunches,
+                                           kLfUnsettledMarginLaunches};
+struct LaunchLog {
+  std::atomic<int32_t> v[kLaunchFields];
+  LaunchLog() {
+    for (auto& x : v) x.store(-1, std::memory_order_relaxed);
+    for (LaunchField f : kLaunchCounters) v[f].store(0, std::memory_order_relaxed);
+  }
+};
+inline LaunchLog g_launch_log;
+inline void launch_note(LaunchField f, int32_t v) { g_launch_log.v[f].store(v, std::memory_order_relaxed); }
+inline void launch_tick(LaunchField f) { g_launch_log.v[f].fetch_add(1, std::memory_order_relaxed); }
 
 constexpr int kBlock = 256;        // prepass points per workgroup (4 waves)
 constexpr int kWave = 64;

@@ -1855,6 +1855,11 @@ hipError_t launch_phi2(const PhiArgs& a, hipStream_t s, hipEvent_t before_values
   const bool narrow = a.d <= 256;
   const int th2 = th2e ? th2e : narrow ? 256 : 1024;
   const int w3 = w3e ? w3e : narrow ? std::min(4, a.wpb) : a.wpb;
+  launch_note(kLfPhiGs, a.gs);
+  launch_note(kLfPhiG, a.G);
+  launch_note(kLfPhiGroupThreads, th1);
+  launch_note(kLfPhiTreeThreads, th2);
+  launch_note(kLfPhiValuesWaves, w3);
   HDPM_LAUNCH(k_phi2_group, dim3((unsigned)(a.T * a.G)), dim3(th1), l1, s, a);
   HDPM_LAUNCH(k_phi2_tree, dim3((unsigned)a.T), dim3(th2), l2, s, a);
   if (before_values) {

@@ -1,7 +1,8 @@
 // switches.hpp -- every HDPM_* environment switch of the engine: the one list of them (31), and the
 // only place that calls getenv.  Host only.  A switch selects a path for A/B runs and diagnosis;
-// the chain is the same with any of them.  (The two other ways to steer the engine are the
-// HDPM_DBG_* bits of hdpm_set_debug and the HDPM_OPT_* options of hdpm_set_option, include/hdpm.h.)
+// the chain is the same with any of them (held to the oracle by tests/test_gpu_switches.py).  (The
+// two other ways to steer the engine are the HDPM_DBG_* bits of hdpm_set_debug and the HDPM_OPT_*
+// options of hdpm_set_option, include/hdpm.h.)
 #pragma once
 #include <algorithm>
 #include <climits>

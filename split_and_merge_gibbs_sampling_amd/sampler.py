@@ -212,6 +212,14 @@ class Engine:
                                             int(ocml), _lib.ptr(out)))
         return out
 
+    def debug_launches(self) -> dict:
+        """Testing: what the process's last launches actually used (include/hdpm.h hdpm_launches:
+        the fast update's group size and workgroup sizes, k_prepass_wide's grid and chunks, the
+        stream generator's jump tables, the last prepass's flags); -1: no such launch yet."""
+        out = _lib.Launches()
+        self._check(self._L.hdpm_debug_launches(self._h, C.byref(out)))
+        return out.as_dict()
+
     def set_phi_device(self, on=True, general: bool = False):
         """update_phi on the device (include/hdpm.h HDPM_OPT_PHI_DEVICE); same chain.  on: True
         (device), False (host job), or "auto" (the default: device for updates of >= 4096 items);
