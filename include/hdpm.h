@@ -599,6 +599,38 @@ int hdpm_predict_new(hdpm_ctx* ctx, const uint8_t* codes, int32_t ny, const int3
                      double* p_new, double* coclass);
 int hdpm_predict_own(hdpm_ctx* ctx, const uint8_t* codes, double* lppd, double* var, double* logcpo);
 int hdpm_predict_loglik(hdpm_ctx* ctx, int32_t s, const uint8_t* codes, int32_t ny, double* ll, double* resp);
+/* Rows with missing attributes: code 0 in a row says "not observed".  Attributes are
+ * independent given the cluster and dhamming sums to 1 over an attribute's codes for every
+ * sigma, so the marginal of a row over its missing attributes is the same urn with those
+ * attributes left out of every sum.  With O(y) the observed attributes of row y:
+ *   ll_k(y) = sum_{j in O} dhamming(y_j, c_kj, sg_kj, m_j), in attribute order (a missing
+ *             attribute adds nothing, which is adding +0.0),
+ *   ll_0(y) = -sum_{j in O} log(m_j), left to right in attribute order, per row,
+ *   w_k = log n_k + ll_k(y), w_0 = log gamma + ll_0(y); lse and r_k as above.
+ *
+ * hdpm_predict_partial: hdpm_predict_new's outputs and rules with these ll_k / ll_0.  A row
+ *   without a 0 gets the bytes hdpm_predict_new gives it; a row of all 0 has w_k = log n_k and
+ *   w_0 = log gamma (lpd = 0).  hdpm_predict_new itself keeps refusing 0.
+ * hdpm_predict_impute: the law of each missing code given the observed codes of its row.
+ *   Entries are the 0 codes of codes[ny x d] in row-major order, n_missing of them; entry e is
+ *   (row y, attribute j).  For level l = 1..m_j, per draw s:
+ *     q_l = r_0 / (double)m_j;  then for k = 1..K_s in cluster order
+ *     q_l = q_l + r_k * (l == c_kj ? exp(match_kj) : exp(mismatch_kj)),
+ *   the exps glibc's.  Over the draws, in draw order, under the running maximum mx of lse that
+ *   lpd's sum keeps (acc = sum_s exp(lse^s - mx)): A_l = q_l at the first draw; at a new
+ *   maximum A_l = A_l * exp(mx_old - lse) + q_l; otherwise A_l = A_l + q_l * exp(lse - mx).
+ *   pmf[e * ld + l - 1] = A_l / acc = sum_s p(y_O, y_j = l | s) / sum_s p(y_O | s) =
+ *   p(y_j = l | y_O, data); slots m_j .. ld-1 are 0.0.  The pmfs of several gaps of one row are
+ *   marginals, not their joint law.  lpd[ny] (may be NULL) has hdpm_predict_partial's bytes.
+ *   n_missing = 0 is accepted and writes only lpd.
+ * No result depends on table_budget_bytes, bit for bit.  HDPM_E_ARG with a message for: a
+ * call before hdpm_predict_build; a code above m_j (row and attribute named); n_missing
+ * different from the count of 0 codes; ld above 255, or below the m_j of a missing attribute
+ * (named); and hdpm_predict_new's refusals for cl and Ka. */
+int hdpm_predict_partial(hdpm_ctx* ctx, const uint8_t* codes, int32_t ny, const int32_t* cl, int32_t Ka, double* lpd,
+                         double* p_new, double* coclass);
+int hdpm_predict_impute(hdpm_ctx* ctx, const uint8_t* codes, int32_t ny, int64_t n_missing, int32_t ld, double* pmf,
+                        double* lpd);
 /* Testing: one draw on the device from log-weights logw[E] (E <= 256) and the uniform rU --
  * the n8:95-102 categorical draw (two_way = 0; *pick = the 0-based index, or -status) or the
  * sm:204-215 two-way draw (two_way = 1, E = 2) -- with the engine's exp, glibc's algorithm

@@ -5565,6 +5565,16 @@ int hdpm_predict_loglik(hdpm_ctx* h, int32_t s, const uint8_t* codes, int32_t ny
   CTX();
   GUARD(return ctx->sum.predict_loglik(s, codes, ny, ll, resp);)
 }
+int hdpm_predict_partial(hdpm_ctx* h, const uint8_t* codes, int32_t ny, const int32_t* cl, int32_t Ka, double* lpd,
+                         double* p_new, double* coclass) {
+  CTX();
+  GUARD(return ctx->sum.predict_partial(codes, ny, cl, Ka, lpd, p_new, coclass);)
+}
+int hdpm_predict_impute(hdpm_ctx* h, const uint8_t* codes, int32_t ny, int64_t n_missing, int32_t ld, double* pmf,
+                        double* lpd) {
+  CTX();
+  GUARD(return ctx->sum.predict_impute(codes, ny, n_missing, ld, pmf, lpd);)
+}
 int hdpm_debug_draw(hdpm_ctx* h, const double* logw, int32_t E, double rU, int32_t two_way, int32_t ocml,
                     int32_t* pick) {
   CTX();

@@ -1,10 +1,12 @@
 // predict_host.hpp -- the host arithmetic of the posterior predictive (hdpm_predict_*), each
 // rule once: the checks of the model and of the recorded parameters, the parameter tables the
 // kernels of predict.hip read, the new-cluster weight, the rows per block and the packing of a
-// block of rows.
+// block of rows, and for rows with missing attributes the code check, the per-row ll_0, the
+// entries, the ld check and imputation's cuts of the rows and of the draws.
 //
-// Plain C++, no HIP: summary_host.cpp includes it, and tests/cpp/predict_host_test.cpp checks
-// it on the host.  A check returns an empty string, or the message of the HDPM_E_ARG refusal.
+// Plain C++, no HIP: summary_host.cpp includes it, and tests/cpp/predict_host_test.cpp and
+// tests/cpp/impute_host_test.cpp check it on the host.  A check returns an empty string, or
+// the message of the HDPM_E_ARG refusal.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -113,6 +115,108 @@ inline void pr_pack_rows(const uint8_t* codes, int64_t r0, int64_t r1, int d, si
       for (int b = 0; b < 4 && 4 * w + b < d; ++b) v |= (uint32_t)codes[r * d + 4 * w + b] << (8 * b);
       cw[(size_t)w * nbp + r] = v;
     }
+}
+
+// ---- rows with missing attributes (hdpm_predict_partial, hdpm_predict_impute): code 0 in a
+// row says that the attribute was not observed
+
+// the first code above m_j among rows x d codes (0 is allowed): its index, or -1
+inline int64_t pr_bad_code_partial(const uint8_t* codes, int64_t rows, int d, const int32_t* att) {
+  for (int64_t i = 0; i < rows; ++i)
+    for (int j = 0; j < d; ++j)
+      if (codes[i * d + j] > att[j]) return i * d + j;
+  return -1;
+}
+inline std::string pr_code_message_partial(int64_t at, int d) {
+  return "predict: codes must lie in 0..attrisize[j], 0 for a missing attribute (row " + std::to_string(at / d) +
+         ", attribute " + std::to_string(at % d) + ")";
+}
+
+// ll_0 of one row: -sum log(m_j) over its observed attributes, left to right; a complete row
+// gives the bits of pr_ll0
+inline double pr_ll0_row(const uint8_t* y, int d, const int32_t* att) {
+  double s = 0.0;
+  for (int j = 0; j < d; ++j)
+    if (y[j] != 0) s = s + std::log((double)att[j]);
+  return -s;
+}
+
+// the missing entries (codes 0) of rows x d codes
+inline int64_t pr_count_missing(const uint8_t* codes, int64_t rows, int d) {
+  int64_t n = 0;
+  for (int64_t q = 0; q < rows * d; ++q) n += codes[q] == 0;
+  return n;
+}
+
+// Entries are numbered in row-major order.  off[b] = the entries of the rows before block b
+// (nb rows each), b = 0 .. blocks, so off[blocks] is their count; returns blocks
+inline size_t pr_missing_offsets(const uint8_t* codes, int64_t ny, int d, size_t nb, int64_t* off) {
+  size_t b = 0;
+  int64_t n = 0;
+  for (int64_t i0 = 0; i0 < ny; i0 += (int64_t)nb, ++b) {
+    off[b] = n;
+    n += pr_count_missing(codes + (size_t)i0 * d, std::min<int64_t>((int64_t)nb, ny - i0), d);
+  }
+  off[b] = n;
+  return b;
+}
+
+// the entries of rows r0 .. r1 - 1 in order, two words each: the row within the block
+// (r - r0) and the attribute
+inline void pr_missing_entries(const uint8_t* codes, int64_t r0, int64_t r1, int d, uint32_t* ent) {
+  for (int64_t r = r0; r < r1; ++r)
+    for (int j = 0; j < d; ++j)
+      if (codes[r * d + j] == 0) {
+        *ent++ = (uint32_t)(r - r0);
+        *ent++ = (uint32_t)j;
+      }
+}
+
+// Imputation cuts the rows into blocks of whole quanta and, within a block, the draws into
+// chunks, so that a block's rows (row_bytes each, one draw's record included), its entries
+// (entry_bytes each) and a chunk's records obey the budget.  qoff: pr_missing_offsets at
+// kPrRowQuantum rows per block.  The quanta of the block that starts at quantum q0: as many
+// as fit (and at most max_entries entries), at least one.
+inline size_t pr_impute_quanta(const int64_t* qoff, size_t nq, size_t q0, size_t budget, size_t row_bytes,
+                               size_t entry_bytes, int64_t max_entries) {
+  size_t n = 1;
+  while (q0 + n < nq) {
+    const int64_t ent = qoff[q0 + n + 1] - qoff[q0];
+    const long double need = (long double)(n + 1) * kPrRowQuantum * row_bytes + (long double)ent * entry_bytes;
+    if (need > (long double)budget || ent > max_entries) break;
+    ++n;
+  }
+  return n;
+}
+// The doubles per row that a block of `rows` rows (whole quanta) with `entries` entries has for
+// the records of a chunk of draws: what the budget leaves after the rows' other staging
+// (row_bytes less the one record of rec1 doubles that it counts) and the entries', spread
+// over the block's own rows; at least rec1 (one draw always goes through), at most `whole`
+// (all the draws).  The record buffer of the block is rows x this.
+inline int64_t pr_impute_rstride(size_t budget, size_t rows, size_t row_bytes, int64_t entries, size_t entry_bytes,
+                                 size_t rec1, int64_t whole) {
+  const long double fixed = (long double)rows * (row_bytes - rec1 * 8) + (long double)entries * entry_bytes;
+  const long double left = (long double)budget > fixed ? (long double)budget - fixed : 0.0L;
+  const int64_t fit = (int64_t)std::min<long double>(left / ((long double)rows * 8), (long double)whole);
+  return std::min<int64_t>(whole, std::max<int64_t>((int64_t)rec1, fit));
+}
+// the end s1 of the chunk of draws that starts at s0: the most draws whose records, off[s1] -
+// off[s0] + 2 (s1 - s0) doubles per row, stay within cap; at least one draw
+inline int pr_draw_chunk(const int64_t* off, int M, int s0, int64_t cap) {
+  int s1 = s0 + 1;
+  while (s1 < M && off[s1 + 1] - off[s0] + 2 * (int64_t)(s1 + 1 - s0) <= cap) ++s1;
+  return s1;
+}
+
+// ld, the slots of a pmf row: at most 255 and at least the m_j of every missing attribute
+inline std::string pr_check_ld(const uint8_t* codes, int64_t rows, int d, const int32_t* att, int ld) {
+  if (ld < 0 || ld > 255) return "predict: ld must be in 0..255";
+  for (int64_t i = 0; i < rows; ++i)
+    for (int j = 0; j < d; ++j)
+      if (codes[i * d + j] == 0 && att[j] > ld)
+        return "predict: ld is " + std::to_string(ld) + ", below attrisize " + std::to_string(att[j]) +
+               " of a missing attribute (row " + std::to_string(i) + ", attribute " + std::to_string(j) + ")";
+  return "";
 }
 
 // partition labels 0..Ka-1, 1 <= Ka <= 255

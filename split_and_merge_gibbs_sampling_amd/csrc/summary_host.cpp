@@ -545,6 +545,7 @@ int Summaries::predict_build(int32_t d, const int32_t* attrisize, double gamma, 
                              const double* centers, const double* sigmas) {
   if (int st = need(false, false)) return st;
   pr_d = 0;
+  pr_emm = false;
   if (!total_cls || !centers || !sigmas) { err = "predict: bad arguments"; return HDPM_E_ARG; }
   err = pr_check_model(d, attrisize, gamma);
   if (!err.empty()) return HDPM_E_ARG;
@@ -592,34 +593,46 @@ int Summaries::predict_build(int32_t d, const int32_t* attrisize, double gamma, 
   return HDPM_OK;
 }
 
-// what every predict call needs: a trace, its parameters, and rows of codes in range
-int Summaries::need_predict(const uint8_t* codes, int64_t rows) {
+// what every predict call needs: a trace, its parameters, and rows of codes in range (partial:
+// 0, a missing attribute, is in range)
+int Summaries::need_predict(const uint8_t* codes, int64_t rows, bool partial) {
   if (int st = need(false, false)) return st;
   if (pr_d == 0) { err = "predict: hdpm_predict_build has not been called"; return HDPM_E_ARG; }
   if (!codes || rows <= 0) { err = "predict: no rows"; return HDPM_E_ARG; }
   std::atomic<int64_t> bad{-1};
   parallel_for(rows, [&](int64_t r0, int64_t r1) {
-    const int64_t at = pr_bad_code(codes + (size_t)r0 * pr_d, r1 - r0, pr_d, pr_att.data());
+    const int64_t at = partial ? pr_bad_code_partial(codes + (size_t)r0 * pr_d, r1 - r0, pr_d, pr_att.data())
+                               : pr_bad_code(codes + (size_t)r0 * pr_d, r1 - r0, pr_d, pr_att.data());
     if (at < 0) return;
     int64_t seen = bad.load(), mine = r0 * pr_d + at;
     while ((seen < 0 || mine < seen) && !bad.compare_exchange_weak(seen, mine)) {}
   });
-  if (bad.load() >= 0) { err = pr_code_message(bad.load(), pr_d); return HDPM_E_ARG; }
+  if (bad.load() >= 0) {
+    err = partial ? pr_code_message_partial(bad.load(), pr_d) : pr_code_message(bad.load(), pr_d);
+    return HDPM_E_ARG;
+  }
   return HDPM_OK;
 }
 
 // Rows in blocks whose device staging (packed codes, scratch columns, outputs) obeys the table
 // budget, against draws s0 .. s1 - 1; each block's results go to the caller as it completes.
 // tab: the tables of the partition (Ka classes) for coclass.  ll / resp: one draw.  A row's
-// results do not depend on the block it falls in.
+// results do not depend on the block it falls in.  miss: code 0 is a missing attribute
+// (k_pr_part; all the draws, no ll / resp).
 void Summaries::predict_blocks(const uint8_t* codes, int64_t ny, int s0, int s1, const uint32_t* tab, int Ka,
-                               double* lpd, double* p_new, double* coclass, double* ll, double* resp) {
+                               double* lpd, double* p_new, double* coclass, double* ll, double* resp, bool miss) {
   const int d = pr_d;
   const size_t nw = (size_t)pr_d4(d) / 4;
   const size_t K1 = (size_t)(pr_off[s0 + 1] - pr_off[s0]);   // the clusters of the one draw of ll / resp
   const size_t per_row = nw * 4 + ((size_t)pr_Kmax + 1) * 8 + (tab ? (size_t)Ka * 8 : 0) + 16 + (ll ? K1 * 8 : 0) +
-                         (resp ? (K1 + 1) * 8 : 0);
+                         (resp ? (K1 + 1) * 8 : 0) + (miss ? 8 : 0);
   const size_t nb = pr_block(tr_budget, per_row, (size_t)ny);
+  std::vector<double> w0;
+  const double log_gamma = std::log(pr_gamma);
+  if (miss) {
+    d_pr_w0.ensure(nb);
+    w0.resize(nb);
+  }
   d_pr_cw.ensure(nw * nb);
   d_pr_w.ensure(((size_t)pr_Kmax + 1) * nb);
   d_pr_out.ensure(2 * nb);
@@ -665,13 +678,135 @@ void Summaries::predict_blocks(const uint8_t* codes, int64_t ny, int s0, int s1,
     a.p_new = p_new ? d_pr_out.p + nb : nullptr;
     a.ll_out = ll ? d_pr_ll.p : nullptr;
     a.resp_out = resp ? d_pr_resp.p : nullptr;
-    HIPCHK(launch_pr_new(a, stream));
+    if (miss) {
+      parallel_for(nr, [&](int64_t r0, int64_t r1) {
+        for (int64_t r = r0; r < r1; ++r)
+          w0[r] = log_gamma + pr_ll0_row(codes + (size_t)(i0 + r) * d, d, pr_att.data());
+      });
+      HIPCHK(hipMemcpyAsync(d_pr_w0.p, w0.data(), (size_t)nr * 8, hipMemcpyHostToDevice, stream));
+      PrPartArgs pa{a, d_pr_w0.p, nullptr, 0, nullptr, 1, 1, s1 - s0};
+      HIPCHK(launch_pr_part(pa, stream));
+    } else {
+      HIPCHK(launch_pr_new(a, stream));
+    }
     if (lpd) HIPCHK(hipMemcpyAsync(lpd + i0, d_pr_out.p, (size_t)nr * 8, hipMemcpyDeviceToHost, stream));
     if (p_new) HIPCHK(hipMemcpyAsync(p_new + i0, d_pr_out.p + nb, (size_t)nr * 8, hipMemcpyDeviceToHost, stream));
     if (tab) take(d_pr_cc.p, (size_t)Ka, i0, nr, coclass);
     if (ll) take(d_pr_ll.p, K1, i0, nr, ll);
     if (resp) take(d_pr_resp.p, K1 + 1, i0, nr, resp);
     HIPCHK(hipStreamSynchronize(stream));
+  }
+}
+
+// Imputation: blocks of rows (whole quanta of 64) and, within a block, chunks of draws, cut so
+// that the block's staging -- packed codes, scratch columns, carried sums, the entries' list,
+// pmf rows and carried sums, and the rows' records of one chunk of draws -- obeys the table
+// budget (at least one quantum and one draw).  Per chunk k_pr_part leaves the records and
+// k_pr_impute folds them into the entries' sums; a lane's walk over all the draws of a block is
+// what a launch costs, so the rows stay together as far as they can and the draws are cut.  No
+// result depends on either cut.
+void Summaries::impute_blocks(const uint8_t* codes, int64_t ny, int ld, double* pmf, double* lpd) {
+  const int d = pr_d, M = tr_M;
+  const size_t q = kPrRowQuantum, nw = (size_t)pr_d4(d) / 4;
+  if (!pr_emm) {
+    const size_t n = (size_t)pr_off[M] * d * 2;
+    d_pr_emm.ensure(n);
+    d_pr_att.ensure((size_t)d);
+    HIPCHK(launch_pr_exp(d_pr_mm.p, (int64_t)n, d_pr_emm.p, stream));
+    HIPCHK(hipMemcpyAsync(d_pr_att.p, pr_att.data(), (size_t)d * 4, hipMemcpyHostToDevice, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    pr_emm = true;
+  }
+  const size_t rec1 = (size_t)pr_Kmax + 2;                    // the longest record of one draw
+  const size_t row_bytes = nw * 4 + ((size_t)pr_Kmax + 1) * 8 + 16 + 8 + 24 + rec1 * 8;
+  const size_t entry_bytes = (size_t)ld * 8 + 24;
+  const size_t nq = ((size_t)ny + q - 1) / q;
+  std::vector<int64_t> qoff(nq + 1);
+  pr_missing_offsets(codes, ny, d, q, qoff.data());
+  struct Block { size_t q0, nq; };
+  std::vector<Block> blk;
+  size_t nb = 0;
+  int64_t nemax = 0;
+  for (size_t q0 = 0; q0 < nq;) {
+    const size_t n = pr_impute_quanta(qoff.data(), nq, q0, tr_budget, row_bytes, entry_bytes, (int64_t)1 << 28);
+    blk.push_back({q0, n});
+    nb = std::max(nb, n * q);
+    nemax = std::max(nemax, qoff[q0 + n] - qoff[q0]);
+    q0 += n;
+  }
+  d_pr_cw.ensure(nw * nb);
+  d_pr_w.ensure(((size_t)pr_Kmax + 1) * nb);
+  d_pr_out.ensure(2 * nb);
+  d_pr_w0.ensure(nb);
+  d_pr_carry.ensure(3 * nb);
+  d_pr_ent.ensure((size_t)nemax * 2);
+  d_pr_pmf.ensure((size_t)nemax * ld);
+  d_pr_st.ensure((size_t)nemax * 2);
+  std::vector<uint32_t> cw(nw * nb), ent((size_t)nemax * 2);
+  std::vector<double> w0(nb);
+  const double log_gamma = std::log(pr_gamma);
+  const int64_t whole = pr_off[M] + 2 * (int64_t)M;           // the record of all the draws
+  for (const Block& b : blk) {
+    const int64_t i0 = (int64_t)(b.q0 * q), nr = std::min<int64_t>((int64_t)(b.nq * q), ny - i0);
+    const int64_t e0 = qoff[b.q0], ne = qoff[b.q0 + b.nq] - e0;
+    parallel_for(nr, [&](int64_t r0, int64_t r1) {
+      pr_pack_rows(codes + (size_t)i0 * d, r0, r1, d, nb, cw.data());
+      for (int64_t r = r0; r < r1; ++r)
+        w0[r] = log_gamma + pr_ll0_row(codes + (size_t)(i0 + r) * d, d, pr_att.data());
+    });
+    pr_missing_entries(codes, i0, i0 + nr, d, ent.data());
+    HIPCHK(hipMemcpyAsync(d_pr_cw.p, cw.data(), cw.size() * 4, hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemcpyAsync(d_pr_w0.p, w0.data(), (size_t)nr * 8, hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemcpyAsync(d_pr_ent.p, ent.data(), (size_t)ne * 8, hipMemcpyHostToDevice, stream));
+    // what the budget leaves for the records, in doubles per row of this block; the buffer
+    // holds this block's rows, not the largest block's
+    const int64_t rstride = pr_impute_rstride(tr_budget, b.nq * q, row_bytes, ne, entry_bytes, rec1, whole);
+    d_pr_r.ensure((size_t)rstride * (b.nq * q));
+    PrPartArgs pa{};
+    PrNewArgs& a = pa.n;
+    a.cw = d_pr_cw.p;
+    a.nrows = nr;
+    a.nbp = (int64_t)nb;
+    a.d = d;
+    a.cen = d_pr_cen.p;
+    a.mm = d_pr_mm.p;
+    a.lognk = d_pr_lognk.p;
+    a.off = d_pr_off.p;
+    a.log_ng = std::log((double)tr_N + pr_gamma);
+    a.w = d_pr_w.p;
+    a.lpd = lpd ? d_pr_out.p : nullptr;
+    pa.w0 = d_pr_w0.p;
+    pa.r = d_pr_r.p;
+    pa.rstride = rstride;
+    pa.carry = d_pr_carry.p;
+    pa.M = M;
+    PrImpArgs ia{};
+    ia.ent = d_pr_ent.p;
+    ia.nent = (int)ne;
+    ia.d = d;
+    ia.ld = ld;
+    ia.st = d_pr_st.p;
+    ia.att = d_pr_att.p;
+    ia.cen = d_pr_cen.p;
+    ia.emm = d_pr_emm.p;
+    ia.off = d_pr_off.p;
+    ia.r = d_pr_r.p;
+    ia.rstride = rstride;
+    ia.pmf = d_pr_pmf.p;
+    for (int s0 = 0; s0 < M;) {
+      const int s1 = pr_draw_chunk(pr_off.data(), M, s0, rstride);
+      a.s0 = ia.s0 = s0;
+      a.s1 = ia.s1 = s1;
+      pa.first = ia.first = s0 == 0;
+      pa.last = ia.last = s1 == M;
+      HIPCHK(launch_pr_part(pa, stream));
+      HIPCHK(launch_pr_impute(ia, stream));
+      s0 = s1;
+    }
+    if (ne > 0)
+      HIPCHK(hipMemcpyAsync(pmf + (size_t)e0 * ld, d_pr_pmf.p, (size_t)ne * ld * 8, hipMemcpyDeviceToHost, stream));
+    if (lpd) HIPCHK(hipMemcpyAsync(lpd + i0, d_pr_out.p, (size_t)nr * 8, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));        // the staging is reused by the next block
   }
 }
 
@@ -743,6 +878,51 @@ int Summaries::predict_loglik(int32_t s, const uint8_t* codes, int32_t ny, doubl
     return HDPM_E_ARG;
   }
   if (ll || resp) predict_blocks(codes, ny, s, s + 1, nullptr, 0, nullptr, nullptr, nullptr, ll, resp);
+  return HDPM_OK;
+}
+
+// Rows with missing attributes (code 0): predict_new's outputs with those attributes left out
+// of every sum
+int Summaries::predict_partial(const uint8_t* codes, int32_t ny, const int32_t* cl, int32_t Ka, double* lpd,
+                               double* p_new, double* coclass) {
+  if (int st = need_predict(codes, ny, true)) return st;
+  if (coclass) {
+    if (!cl) { err = "predict: coclass needs a partition of the training points"; return HDPM_E_ARG; }
+    err = pr_check_classes(cl, tr_N, Ka);
+    if (!err.empty()) return HDPM_E_ARG;
+  }
+  if (!lpd && !p_new && !coclass) return HDPM_OK;
+  if (!coclass) {
+    predict_blocks(codes, ny, 0, tr_M, nullptr, 0, lpd, p_new, nullptr, nullptr, nullptr, true);
+    return HDPM_OK;
+  }
+  std::vector<double> na((size_t)Ka, 0.0);
+  for (int i = 0; i < tr_N; ++i) na[cl[i]] += 1.0;
+  d_pr_na.ensure((size_t)Ka);
+  HIPCHK(hipMemcpyAsync(d_pr_na.p, na.data(), (size_t)Ka * 8, hipMemcpyHostToDevice, stream));
+  blocks({cl, 0, 1}, Ka, false, false, false, [&](int, int, const uint8_t*) {
+    predict_blocks(codes, ny, 0, tr_M, d_tr_tab.p, Ka, lpd, p_new, coclass, nullptr, nullptr, true);
+  });
+  return HDPM_OK;
+}
+
+// The law of every missing code given its row's observed ones: pmf[n_missing x ld], entries in
+// row-major order of the codes; lpd as predict_partial gives it
+int Summaries::predict_impute(const uint8_t* codes, int32_t ny, int64_t n_missing, int32_t ld, double* pmf,
+                              double* lpd) {
+  if (int st = need_predict(codes, ny, true)) return st;
+  const int64_t have = pr_count_missing(codes, ny, pr_d);
+  if (n_missing != have) {
+    err = "predict: n_missing is " + std::to_string(n_missing) + " but the rows hold " + std::to_string(have) +
+          " missing codes";
+    return HDPM_E_ARG;
+  }
+  err = pr_check_ld(codes, ny, pr_d, pr_att.data(), ld);
+  if (!err.empty()) return HDPM_E_ARG;
+  if (have > 0 && !pmf) { err = "predict: no pmf"; return HDPM_E_ARG; }
+  if (have == 0 && !lpd) return HDPM_OK;
+  if (have == 0) predict_blocks(codes, ny, 0, tr_M, nullptr, 0, lpd, nullptr, nullptr, nullptr, nullptr, true);
+  else impute_blocks(codes, ny, ld, pmf, lpd);
   return HDPM_OK;
 }
 

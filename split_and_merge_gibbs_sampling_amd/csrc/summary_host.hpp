@@ -42,6 +42,9 @@ class Summaries {
                   double* coclass);
   int predict_own(const uint8_t* codes, double* lppd, double* var, double* logcpo);
   int predict_loglik(int32_t s, const uint8_t* codes, int32_t ny, double* ll, double* resp);
+  int predict_partial(const uint8_t* codes, int32_t ny, const int32_t* cl, int32_t Ka, double* lpd, double* p_new,
+                      double* coclass);
+  int predict_impute(const uint8_t* codes, int32_t ny, int64_t n_missing, int32_t ld, double* pmf, double* lpd);
 
  private:
   hipStream_t& stream;
@@ -95,11 +98,20 @@ class Summaries {
   std::vector<int32_t> pr_att;
   int pr_d = 0, pr_Kmax = 0;   // pr_d == 0: no parameters
   double pr_gamma = 0.0, pr_w0 = 0.0;
+  // Rows with missing attributes add w_0 per row.  Imputation adds the exps of the pairs and
+  // attrisize on the device (built at its first call after predict_build: pr_emm) and, per
+  // block of rows, a record per row (lse and r_k of a chunk of draws), the rows' sums carried
+  // between chunks, and the entries' list, pmf rows and carried (mx, acc)
+  DevBuf<double> d_pr_w0, d_pr_emm, d_pr_r, d_pr_pmf, d_pr_carry, d_pr_st;
+  DevBuf<uint32_t> d_pr_ent;
+  DevBuf<int32_t> d_pr_att;
+  bool pr_emm = false;
 
   struct Cands;
-  int need_predict(const uint8_t* codes, int64_t rows);
+  int need_predict(const uint8_t* codes, int64_t rows, bool partial = false);
   void predict_blocks(const uint8_t* codes, int64_t ny, int s0, int s1, const uint32_t* tab, int Ka, double* lpd,
-                      double* p_new, double* coclass, double* ll, double* resp);
+                      double* p_new, double* coclass, double* ll, double* resp, bool miss = false);
+  void impute_blocks(const uint8_t* codes, int64_t ny, int ld, double* pmf, double* lpd);
   int need(bool groups, bool tree);
   int check(const int32_t* cls, int ncand, int* Ka);
   template <class F>

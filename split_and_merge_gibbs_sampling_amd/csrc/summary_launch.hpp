@@ -1,7 +1,7 @@
 // summary_launch.hpp -- launchers of the posterior-summary kernels: posterior.hip
 // (launch_psm, launch_vi_terms), trace_summary.hip (launch_tr_pack .. launch_tr_reduce,
 // launch_tg_*) and trace_uncertainty.hip (launch_tr_transpose, launch_tr_affinity,
-// launch_tr_cross) and predict.hip (launch_pr_new, launch_pr_own).  Included by the units that
+// launch_tr_cross) and predict.hip (launch_pr_new .. launch_pr_impute).  Included by the units that
 // define them and by summary_host.cpp, their only caller.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -79,7 +79,42 @@ struct PrOwnArgs {
   double* var;
   double* logcpo;
 };
+// Rows with missing attributes (code 0).  k_pr_part is k_pr_new with the missing attributes
+// left out of every sum and a w_0 per row (n.w0, n.ll_out and n.resp_out are not read); for
+// k_pr_impute it leaves, per row of the block, a record of up to rstride doubles: draw s at
+// off[s] - off[s0] + 2 (s - s0), holding lse, r_0, r_1 .. r_K.  A wave of k_pr_impute reads
+// a draw of its row as one contiguous piece.  The draws may come in chunks s0 .. s1 - 1 of
+// 0 .. M - 1, one launch each in order: a row's running sums (lpd's maximum and sum, p_new's
+// sum) then pass through carry, double for double, and cc keeps the fold's.
+struct PrPartArgs {
+  PrNewArgs n;
+  const double* w0;                 // nbp: log gamma + ll_0 of the row
+  double* r;                        // nbp x rstride, or null
+  int64_t rstride;                  // at least off[s1] - off[s0] + 2 (s1 - s0)
+  double* carry;                    // 3 x nbp, or null when first and last
+  int first, last, M;               // s0 == 0; s1 == M; the draws in all
+};
+// k_pr_impute: a wave per missing entry, lanes over the levels.  ent holds (row of the block,
+// attribute) per entry; emm the exps of mm; the draws are the chunk s0 .. s1 - 1 that k_pr_part
+// just left in r.  Between chunks A_l stays in the entry's pmf row and (mx, acc) in st.
+constexpr int kPrImpWaves = 4;      // entries of a workgroup
+struct PrImpArgs {
+  const uint32_t* ent;
+  int nent;
+  int d, s0, s1, first, last, ld;   // first: s0 == 0; last: s1 == M
+  double* st;                       // 2 x nent
+  const int32_t* att;               // d
+  const uint8_t* cen;
+  const double* emm;
+  const int64_t* off;
+  const double* r;                  // the rows' records as k_pr_part left them
+  int64_t rstride;
+  double* pmf;                      // nent x ld
+};
 hipError_t launch_pr_new(const PrNewArgs& a, hipStream_t s);
 hipError_t launch_pr_own(const PrOwnArgs& a, hipStream_t s);
+hipError_t launch_pr_part(const PrPartArgs& a, hipStream_t s);
+hipError_t launch_pr_exp(const double* x, int64_t n, double* out, hipStream_t s);
+hipError_t launch_pr_impute(const PrImpArgs& a, hipStream_t s);
 
 }  // namespace hdpm

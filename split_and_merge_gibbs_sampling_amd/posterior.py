@@ -327,8 +327,9 @@ class Predictive:
     same saved iterations; ``attrisize`` and ``gamma`` are the chain's.  Label k of draw s
     names row k of that draw's parameters, so the saved labels of draw s must be exactly
     0..K_s-1 (ValueError otherwise): ``LabelTrace``'s relabelling is then the identity.  Rows
-    hold codes 1..m_j.  The trace's ``table_budget`` bounds the device staging of a block of
-    rows and changes no result."""
+    hold codes 1..m_j; ``partial`` and ``impute`` alone take 0 for a missing attribute.  The
+    trace's ``table_budget`` bounds the device staging of a block of rows and changes no
+    result."""
 
     def __init__(self, trace: LabelTrace, centers, sigmas, attrisize, gamma: float):
         if not isinstance(trace, LabelTrace):
@@ -366,7 +367,7 @@ class Predictive:
         """lpd[y]: the log posterior predictive density of each row of ``Y``."""
         return self._new(Y, None, True, False)[0]
 
-    def _new(self, Y, cl, want_lpd, want_pnew, Ka=None):
+    def _new(self, Y, cl, want_lpd, want_pnew, Ka=None, call="hdpm_predict_new"):
         y = self._rows(Y)
         eng = self.trace.eng
         lpd = np.zeros(y.shape[0]) if want_lpd else None
@@ -381,8 +382,7 @@ class Predictive:
             Ka = int(c.max()) + 1
         if cl is not None:
             co = np.zeros((y.shape[0], max(int(Ka), 0)))
-        eng._check(eng._L.hdpm_predict_new(eng._h, ptr(y), y.shape[0], ptr(c), int(Ka or 0), ptr(lpd), ptr(pn),
-                                           ptr(co)))
+        eng._check(getattr(eng._L, call)(eng._h, ptr(y), y.shape[0], ptr(c), int(Ka or 0), ptr(lpd), ptr(pn), ptr(co)))
         return lpd, pn, co
 
     def classify(self, Y, cl, Ka: int | None = None):
@@ -394,6 +394,31 @@ class Predictive:
         posterior probability that y opens a cluster of its own."""
         _, pn, co = self._new(Y, cl, False, True, Ka)
         return np.argmax(co, axis=1), co, pn
+
+    def partial(self, Y, cl=None, Ka: int | None = None):
+        """(lpd, p_new, coclass | None) of rows in which code 0 marks a missing attribute:
+        ``density`` and ``classify``'s numbers from the observed attributes alone (the missing
+        ones are summed out exactly: they drop out of every sum).  A row without a 0 gets the
+        bytes of ``density`` / ``classify``; ``cl`` and ``Ka`` as in ``classify``."""
+        return self._new(Y, cl, True, True, Ka, call="hdpm_predict_partial")
+
+    def impute(self, Y, ld: int | None = None):
+        """(rows, attrs, pmf, mode, lpd): the posterior law of every missing code (0) of ``Y``
+        given the observed codes of its row.  Entry e is (rows[e], attrs[e]), in row-major
+        order; pmf[e, l - 1] = p(y_j = l | observed, data) for l = 1..m_j and 0.0 beyond
+        (``ld`` slots, by default the largest m_j among the missing attributes); mode[e] is the
+        first arg-max level, 1-based; lpd[y] is ``partial``'s.  The pmfs of several gaps of one
+        row are marginals, not their joint law."""
+        y = self._rows(Y)
+        eng = self.trace.eng
+        rows, attrs = np.nonzero(y == 0)
+        if ld is None:
+            ld = int(self.att[attrs].max()) if rows.size else 0
+        pmf, lpd = np.zeros((rows.size, int(ld))), np.zeros(y.shape[0])
+        eng._check(eng._L.hdpm_predict_impute(eng._h, ptr(y), y.shape[0], int(rows.size), int(ld),
+                                              ptr(pmf) if rows.size else None, ptr(lpd)))
+        mode = np.argmax(pmf, axis=1) + 1 if rows.size and ld else np.zeros(rows.size, np.int64)
+        return rows, attrs, pmf, mode, lpd
 
     def pointwise(self, X):
         """(lppd, var, logcpo) of the N training rows ``X`` (the rows the chain ran on): per
