@@ -583,17 +583,20 @@ struct SmWork {
 };
 
 // A window of the R random stream generated on the device (k_mt_gen), starting at the
-// host stream position start_pos.  Two windows alternate: while a sweep consumes one, the
-// next window is generated from the state where that sweep's draws end, so the device
-// generator runs concurrently with the sweep and the host-side update_phi draws.
+// host stream position start_pos.  Two windows alternate: while the sweeps consume one, the
+// next window is generated from a state near that window's end (window_overlap), so the
+// device generator runs concurrently with the sweep and the host-side update_phi draws.
 struct RngWindow {
-  DevBuf<uint32_t> raw, arrays, init;
-  const uint32_t* init_src = nullptr;   // initial array on the device (init.p or a block of another window)
+  DevBuf<uint32_t> raw, init;
+  // initial array on the device: init.p, or a block of another window's raw words in place
+  // (init_tempered: 624 outputs, the array behind them by mt_untemper); h_init mirrors it
+  const uint32_t* init_src = nullptr;
+  bool init_tempered = false;
   PinBuf<uint32_t> h_init;
   uint64_t start_pos = 0, epoch = ~0ull;
   int64_t count = 0;
-  int mti0 = 624, nblocks = 0, export_from = 1;
-  int64_t export_after = 0;
+  int64_t out_len = 0;                  // words stored in raw: count's last block whole
+  int mti0 = 624, nblocks = 0;
   hipEvent_t done = nullptr;
   bool valid = false;
   uint64_t gen = 0;                     // launches of this window (a pipelined sweep waited on one)
@@ -641,6 +644,7 @@ struct Ctx {
     hipEvent_t ev = nullptr;
     PinBuf<uint32_t> arr;
     const uint32_t* host_src = nullptr;
+    bool tempered = false;                // arr / host_src hold the block's outputs, not the array
     const uint32_t* from_raw = nullptr;   // tempered words of the state's block (phi_device_prefetch)
     int mti = 0;
   } pend;
@@ -1029,29 +1033,31 @@ struct Ctx {
     } else {
       HIPCHK(hipEventSynchronize(pend.ev));
       mark("rs.state");
-      std::memcpy(rng.mt, pend.host_src ? pend.host_src : pend.arr.p, sizeof(rng.mt));
+      const uint32_t* src = pend.host_src ? pend.host_src : pend.arr.p;
+      if (pend.tempered)
+        for (int i = 0; i < 624; ++i) rng.mt[i] = mt_untemper(src[i]);
+      else
+        std::memcpy(rng.mt, src, sizeof(rng.mt));
     }
     rng.mti = pend.mti;
     pend.active = false;
   }
   void rng_drop_pending() { pend.active = false; }
 
-  void size_window(RngWindow& W, int64_t count, int64_t export_after) {
+  void size_window(RngWindow& W, int64_t count) {
     const int head = W.mti0 >= 624 ? 0 : 624 - W.mti0;
     W.nblocks = count > head ? (int)((count - head + 623) / 624) : 0;
     W.count = count;
+    // the last block is stored whole: the state at any position of the window past its
+    // initial array is a block of raw (locate)
+    W.out_len = count > head ? head + (int64_t)W.nblocks * 624 : count;
     // sized for any start offset (the block count varies with it), so a window of a given
     // length is never reallocated -- a free would synchronise the device
     // (with headroom: the span grows a little when the draws between sweeps do)
-    if (W.raw.n < (size_t)count) W.raw.ensure((size_t)count + (size_t)count / 4);
-    const size_t aw = (size_t)((count + 623) / 624 + 2) * 624;
-    if (W.arrays.n < aw) W.arrays.ensure(aw + aw / 4);
+    if (W.raw.n < (size_t)count + 624) W.raw.ensure((size_t)count + (size_t)count / 4 + 624);
     W.init.ensure(624);
     W.h_init.ensure(624);
     if (!W.done) HIPCHK(hipEventCreateWithFlags(&W.done, hipEventDisableTiming));
-    // the host adopts states only at or after `export_after` draws into the window
-    W.export_from = (int)std::max<int64_t>(1, (export_after - head) / 624 - 1);
-    W.export_after = export_after;
   }
   // a generator launch may overwrite buffers the copy stream still reads
   void gstream_after_copies() {
@@ -1062,7 +1068,8 @@ struct Ctx {
   void run_window(RngWindow& W) {
     ensure_jump(W.count);
     const bool multi = mt_G > 1 && W.count >= (int64_t)mt_G * 624 * 8;
-    MtGenArgs a{W.init_src ? W.init_src : W.init.p, W.mti0, W.count, W.raw.p, W.arrays.p, W.nblocks, W.export_from,
+    MtGenArgs a{W.init_src ? W.init_src : W.init.p, W.mti0, W.count, W.raw.p, W.out_len, W.nblocks,
+                W.init_src && W.init_tempered ? 1 : 0,
                 multi ? d_jpoly.p : nullptr, d_jidx.p, d_joff.p, mt_bpg, multi ? mt_G : 1};
     launch_note(kLfMtG, mt_G);
     launch_note(kLfMtBpg, mt_bpg);
@@ -1077,7 +1084,7 @@ struct Ctx {
   }
 
   // Window starting at the host stream's current state.
-  void launch_window(RngWindow& W, int64_t count, int64_t export_after = 0) {
+  void launch_window(RngWindow& W, int64_t count) {
     rng_sync();
     if (rng.mti == 625) {  // never seeded: R seeds with 4357 (MT_sgenrand) on the first draw
       uint32_t seed = 4357;
@@ -1094,18 +1101,18 @@ struct Ctx {
     W.mti0 = rng.mti;
     W.start_pos = rng.pos;
     W.epoch = rng.epoch;
-    size_window(W, count, export_after);
+    size_window(W, count);
     // the other window's buffers too, now: its first launch comes mid-chain, where an
     // allocation would stall the iteration
     RngWindow& O = (&W == &win[0]) ? win[1] : win[0];
     if (O.raw.n < W.raw.n) O.raw.ensure(W.raw.n);
-    if (O.arrays.n < W.arrays.n) O.arrays.ensure(W.arrays.n);
     O.init.ensure(624);
     O.h_init.ensure(624);
     if (!O.done) HIPCHK(hipEventCreateWithFlags(&O.done, hipEventDisableTiming));
     std::memcpy(W.h_init.p, rng.mt, sizeof(rng.mt));
     HIPCHK(hipMemcpyAsync(W.init.p, W.h_init.p, 624 * 4, hipMemcpyHostToDevice, gstream));
     W.init_src = W.init.p;
+    W.init_tempered = false;
     run_window(W);
   }
 
@@ -1122,12 +1129,17 @@ struct Ctx {
     const uint64_t b = 1 + (r - head) / 624, k = (r - head) % 624;
     *blk = (int64_t)(k == 0 ? b - 1 : b);
     *mti = k == 0 ? 624 : (int)k;
-    if (*blk != 0 && *blk < W.export_from) throw HipError{hipErrorInvalidValue, "rng window export"};
+    if (*blk > W.nblocks) throw HipError{hipErrorInvalidValue, "rng window block"};
+  }
+  // Block blk >= 1 of window W: its 624 outputs in raw (the state array X_blk tempered)
+  static const uint32_t* block_words(const RngWindow& W, int64_t blk) {
+    const int64_t head = W.mti0 >= 624 ? 0 : 624 - W.mti0;
+    return W.raw.p + head + (blk - 1) * 624;
   }
 
   // Window Wn starting at position `target` of window Ws, initialised on the device from
-  // Ws's exported arrays (no host round trip).
-  void launch_window_from(RngWindow& Wn, RngWindow& Ws, uint64_t target, int64_t count, int64_t export_after) {
+  // the block of Ws's words that holds `target` (no host round trip).
+  void launch_window_from(RngWindow& Wn, RngWindow& Ws, uint64_t target, int64_t count) {
     int64_t blk;
     int mti;
     locate(Ws, target, &blk, &mti);
@@ -1135,15 +1147,19 @@ struct Ctx {
     Wn.start_pos = target;
     Wn.epoch = rng.epoch;
     gstream_after_copies();
-    size_window(Wn, count, export_after);
+    size_window(Wn, count);
     if (blk == 0) {
-      // inside Ws's initial array, which may live in Wn's own exports: copy it out first
+      // inside Ws's initial array, which may live in Wn's own words: copy it out first
+      // (defensive: device_draws starts a window at least a request past its source's start
+      // and a span is 4.2M words or more, so no caller lands here today)
       HIPCHK(hipMemcpyAsync(Wn.init.p, Ws.init_src ? Ws.init_src : Ws.init.p, 624 * 4, hipMemcpyDeviceToDevice,
                             gstream));
       Wn.init_src = Wn.init.p;
+      Wn.init_tempered = Ws.init_src && Ws.init_tempered;
     } else {
-      // read in place: Ws's exports are rewritten only by a later launch on this stream
-      Wn.init_src = Ws.arrays.p + (blk - 1) * 624;
+      // read in place: Ws's words are rewritten only by a later launch on this stream
+      Wn.init_src = block_words(Ws, blk);
+      Wn.init_tempered = true;
     }
     HIPCHK(hipMemcpyAsync(Wn.h_init.p, Wn.init_src, 624 * 4, hipMemcpyDeviceToHost, gstream));
     run_window(Wn);
@@ -1224,8 +1240,7 @@ struct Ctx {
   }
 
   bool covers(const RngWindow& W, uint64_t p, int64_t n) const {
-    return W.valid && W.epoch == rng.epoch && W.start_pos <= p && p + n <= W.start_pos + (uint64_t)W.count &&
-           p + n >= W.start_pos + (uint64_t)W.export_after;
+    return W.valid && W.epoch == rng.epoch && W.start_pos <= p && p + n <= W.start_pos + (uint64_t)W.count;
   }
 
   // The index (1..624; 0: none) of position p in its block of the stream (the same block edges
@@ -1273,10 +1288,12 @@ struct Ctx {
     HIPCHK(hipStreamWaitEvent(cstream, W.done, 0));
     if (blk == 0) {
       pend.host_src = W.h_init.p;     // valid once W's init has landed (W.done)
+      pend.tempered = W.init_tempered;
     } else {
       pend.arr.ensure(624);
       pend.host_src = nullptr;
-      HIPCHK(hipMemcpyAsync(pend.arr.p, W.arrays.p + (blk - 1) * 624, 624 * 4, hipMemcpyDeviceToHost, cstream));
+      pend.tempered = true;
+      HIPCHK(hipMemcpyAsync(pend.arr.p, block_words(W, blk), 624 * 4, hipMemcpyDeviceToHost, cstream));
     }
     HIPCHK(hipEventRecord(pend.ev, cstream));
     pend.mti = mti;
@@ -1385,25 +1402,42 @@ struct Ctx {
   //
   // Windows span many sweeps (`window_span`): one jump-ahead + twist launch serves ~16
   // sweeps and the draws between them, instead of one launch (dominated by the jump) per
-  // sweep.  The next window is launched from the end of the current sweep's draws when the
-  // current one has fewer than `kLead` sweeps' worth left, so it is ready well before use.
+  // sweep.  The next window is launched when the current one has fewer than `kLead` sweeps'
+  // worth left, so it is ready well before use; it starts `window_overlap` words before the
+  // current one's end (never before the end of this sweep's draws).
   // (a window takes ~0.5 ms to generate at C5, several sweeps' time: started 8 sweeps
   // ahead, it is done before the first draw from it)
   static constexpr int kLead = 8;
   int64_t window_span(int64_t n) const {
     // independent of cmax unless the draws between sweeps outgrow its allowance, so the
     // span (window buffers, jump tables) stays fixed
-    const int64_t cap = (int64_t)1 << 27;      // 512 MB of draws (+ 512 MB of exported arrays)
+    const int64_t cap = (int64_t)1 << 27;      // 512 MB of draws
     return std::max(n + cmax, std::min<int64_t>(16 * (n + (1 << 18)), cap));
   }
+  // Every stretch of the stream is generated once: the next window starts `window_overlap`
+  // words before the current one ends, not at the current position.  The overlap is the
+  // longest stretch a single consumer asks one window for -- a sweep's draws with the
+  // allowance behind them, or the longest request seen (note_request: device_draws,
+  // window_at, pre_enqueue's span) -- plus the update's slices around it (phi_device_prefetch
+  // from the start of a block, phi_lookahead's look_words).  A request no longer than that
+  // which runs past the current window's end starts inside the next one, so one of the two
+  // holds it whole at every position, as when the windows overlapped by half.  The longest
+  // request is that of the current window's lifetime (device_draws starts it over at every
+  // launch), so one long request -- a restricted Gibbs chain's -- widens one overlap, not all.
+  int64_t req_max = 0;
+  void note_request(int64_t len) { req_max = std::max(req_max, len); }
+  int64_t window_overlap(int64_t n) const {
+    return std::min(window_span(n) / 2, std::max(n + cmax, req_max) + 2 * phi_prefetch + 8 * 624);
+  }
   const uint32_t* device_draws(int64_t n) {
+    note_request(n);
     RngWindow* W = nullptr;
     for (auto& w : win)
       if (covers(w, rng.pos, n) && (!W || w.start_pos < W->start_pos)) W = &w;
     if (!W) {
       if (win[0].valid || win[1].valid) cmax = std::min<int64_t>(cmax * 2, 1 << 26);
       W = &win[0];
-      launch_window(*W, window_span(n), n);
+      launch_window(*W, window_span(n));
       stats.rng_windows_fresh++;
     }
     mark("dd.window");
@@ -1419,8 +1453,11 @@ struct Ctx {
     RngWindow* other = (W == &win[0]) ? &win[1] : &win[0];
     const bool ahead = other->valid && other->epoch == rng.epoch && other->start_pos > W->start_pos;
     const uint64_t wend = W->start_pos + (uint64_t)W->count;
-    if (!ahead && wend < target + (uint64_t)(kLead * (n + cmax)))
-      launch_window_from(*other, *W, target, window_span(n), n);
+    if (!ahead && wend < target + (uint64_t)(kLead * (n + cmax))) {
+      const uint64_t ov = (uint64_t)window_overlap(n);
+      launch_window_from(*other, *W, wend > target + ov ? wend - ov : target, window_span(n));
+      req_max = 0;
+    }
     return p;
   }
 
@@ -1951,7 +1988,7 @@ struct Ctx {
       }
       pg.raw.ensure(count);
       const int nblocks = count > head ? (int)((count - head + 623) / 624) : 0;
-      MtGenArgs ma{pg.init.p, mti0, count, pg.raw.p, nullptr, nblocks, 0x7fffffff,
+      MtGenArgs ma{pg.init.p, mti0, count, pg.raw.p, count, nblocks, 0,
                    multi ? pg.jpoly.p : nullptr, pg.jidx.p, pg.joff.p, pg.bpg, multi ? G : 1};
       HIPCHK(launch_mt_gen(ma, stream));
       HIPCHK(hipStreamSynchronize(stream));
@@ -2547,6 +2584,7 @@ struct Ctx {
     const bool dev = !host_spec();
     const uint64_t lo = dev ? dspec.pos : spec.pos;
     const uint64_t hi = lo + (uint64_t)(dev ? dspec.pl.need : 2 * phi_prefetch) + (uint64_t)n * (m + 1);
+    note_request((int64_t)(hi - lo));
     int whole = -1;                      // the earliest window holding all of it
     for (int k = 0; k < 2; ++k) {
       const RngWindow& w = win[k];
@@ -3842,20 +3880,13 @@ struct Ctx {
     phd.ready = true;
   }
 
-  // The window holding [pos, pos + n) and able to hand the host its state after it.
+  // The window holding [pos, pos + n) (any position of it can hand the host its state).
   RngWindow* window_at(uint64_t pos, int64_t n) {
+    note_request(n);
     RngWindow* W = nullptr;
     for (auto& w_ : win)
       if (covers(w_, pos, n) && (!W || w_.start_pos < W->start_pos)) W = &w_;
     return W;
-  }
-  bool can_adopt(const RngWindow& W, uint64_t target) const {
-    const uint64_t r = target - W.start_pos;
-    const uint64_t head = W.mti0 >= 624 ? 0 : 624 - W.mti0;
-    if (r < head) return true;
-    const uint64_t b = 1 + (r - head) / 624, k = (r - head) % 624;
-    const int64_t blk = (int64_t)(k == 0 ? b - 1 : b);
-    return blk == 0 || blk >= W.export_from;
   }
 
   // update_phi (cf:511-591) of the labels in mask on the device.  Returns kOk when committed
@@ -4293,7 +4324,7 @@ struct Ctx {
       std::fprintf(stderr, "[phi] T %d nw %d Wc %d status %d cons %lld dts0 %lld F[0][0] %d valid(t=0) %d rate %.4f sdev %.4f\n",
                    T, pl.nw, pl.Wc, status, (long long)cons, (long long)dts[0], F[0], valid0, pl.rate, pl.sdev);
     }
-    if (status != kPhiOk || cons <= 0 || !can_adopt(*W, target)) {
+    if (status != kPhiOk || cons <= 0) {
       phd_release(stream);
       phi_note_handback(status, true);
       if (status == kPhiOk) stats.phi_device_last_status = -1;
@@ -4532,7 +4563,7 @@ struct Ctx {
       return -1;
     }
     if (!followed && (status != kPhiOk || cons <= 0 || !dspec.W || dspec.W->gen != dspec.wgen ||
-                      !can_adopt(*dspec.W, target) || !covers(*dspec.W, rng.pos, dspec.pl.need))) {
+                      !covers(*dspec.W, rng.pos, dspec.pl.need))) {
       phi_note_handback(status, false);
       return kPhiHandedBack;
     }
@@ -4616,7 +4647,7 @@ struct Ctx {
     stats.phi_device_last_status = status;
     const int64_t cons = res.cons();
     const uint64_t target = rng.pos + (uint64_t)cons;
-    if (status != kPhiOk || cons <= 0 || !can_adopt(*W, target)) {
+    if (status != kPhiOk || cons <= 0) {
       if (status == kPhiOk) stats.phi_device_last_status = -1;
       if (sw::get<sw::PHI_TRACE>())
         std::fprintf(stderr, "[phi sm] T %d items %lld need %lld nw %d p_rej %.4f status %d cons %lld counts %d %d\n", T,

@@ -5242,10 +5242,28 @@ __device__ __forceinline__ uint32_t mt_twist_elem(const uint32_t* o, int k) {
   return mt_f(o[623], g1(0), g2(396));
 }
 
+// Inverse of mt_temper: the state word behind an output (rmath.hpp mt_untemper).
+__device__ __forceinline__ uint32_t mt_untemper(uint32_t y) {
+  y ^= y >> 18;
+  y ^= (y << 15) & 0xefc60000u;
+  uint32_t r = y;
+#pragma unroll
+  for (int i = 0; i < 5; ++i) r = y ^ ((r << 7) & 0x9d2c5680u);
+  y = r;
+#pragma unroll
+  for (int i = 0; i < 3; ++i) r = y ^ (r >> 11);
+  return r;
+}
+// Word t of the initial array X_0 (given as it is, or as its outputs)
+__device__ __forceinline__ uint32_t mt_init_word(const MtGenArgs& a, int t) {
+  const uint32_t w = a.init[t];
+  return a.init_tempered ? mt_untemper(w) : w;
+}
+
 __global__ __launch_bounds__(640) void k_mt_gen(MtGenArgs a) {
   __shared__ uint32_t buf[2][624];
   const int t = threadIdx.x;
-  if (t < 624) buf[0][t] = a.init[t];
+  if (t < 624) buf[0][t] = mt_init_word(a, t);
   __syncthreads();
   const int head = a.mti0 >= 624 ? 0 : 624 - a.mti0;
   for (int r = t; r < head && r < a.count; r += 640) a.out[r] = mt_temper(buf[0][a.mti0 + r]);
@@ -5259,9 +5277,8 @@ __global__ __launch_bounds__(640) void k_mt_gen(MtGenArgs a) {
     // LDS-only barrier: the global stores of earlier blocks stay in flight
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
     if (t < 624) {
-      if (b >= a.export_from) a.arrays[(int64_t)(b - 1) * 624 + t] = nv;
       const int64_t r = head + (int64_t)(b - 1) * 624 + t;
-      if (r < a.count) a.out[r] = mt_temper(nv);
+      if (r < a.out_len) a.out[r] = mt_temper(nv);
     }
     cur ^= 1;
   }
@@ -5286,9 +5303,9 @@ __global__ __launch_bounds__(640) void k_mt_gen_multi(MtGenArgs a) {
   const bool last = (g == a.G - 1) || ((int64_t)(g + 1) * a.bpg > b_last);
   const int64_t b_end = last ? b_last + 1 : (int64_t)(g + 1) * a.bpg;
   if (g == 0) {
-    if (t < 624) buf0[t] = a.init[t];
+    if (t < 624) buf0[t] = mt_init_word(a, t);
   } else {
-    if (t < 624) seq[t] = t == 0 ? (a.init[0] & 0x80000000u) : a.init[t];
+    if (t < 624) seq[t] = t == 0 ? (mt_init_word(a, 0) & 0x80000000u) : mt_init_word(a, t);
     for (int blk = 1; blk < 33; ++blk) {
       asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
       if (t < 624) seq[blk * 624 + t] = mt_twist_elem(seq + (blk - 1) * 624, t);
@@ -5338,9 +5355,8 @@ __global__ __launch_bounds__(640) void k_mt_gen_multi(MtGenArgs a) {
       nv = cur[t];
     }
     if (t < 624) {
-      if (b >= 1 && b >= a.export_from) a.arrays[(b - 1) * 624 + t] = nv;
       const int64_t r = b * 624 + t - a.mti0;
-      if (r >= 0 && r < a.count) a.out[r] = mt_temper(nv);
+      if (r >= 0 && r < a.out_len) a.out[r] = mt_temper(nv);
     }
   }
 }

@@ -690,16 +690,18 @@ enum PhiStatus { kPhiOk = 0, kPhiWalker = 1, kPhiBisect = 2, kPhiAmbig = 3, kPhi
 
 // R's Mersenne-Twister stream on the device (one workgroup, one twist per barrier).
 // Output r >= 0 continues the host state (X_0, mti0): the first 624 - mti0 outputs temper
-// X_0[mti0..623]; then block b >= 1 tempers X_b = twist^b(X_0).  Every X_b is exported so
-// the host can adopt the state at any later position.
+// X_0[mti0..623]; then block b >= 1 tempers X_b = twist^b(X_0).  No state array is stored:
+// X_b is block b's 624 outputs untempered, so whoever needs the state at a later position
+// (the host, the next window) reads that block of `out`.  For that the last block may be
+// written whole, past `count` (out_len).
 struct MtGenArgs {
-  const uint32_t* init;   // X_0 (624 words)
+  const uint32_t* init;   // X_0 (624 words); its tempered outputs when init_tempered
   int mti0;
   int64_t count;
   uint32_t* out;          // count raw outputs
-  uint32_t* arrays;       // X_b for b >= export_from (index b - 1); earlier blocks not stored
+  int64_t out_len;        // outputs stored: count, or through the end of count's block
   int nblocks;
-  int export_from;
+  int init_tempered;      // init holds a block of another launch's outputs: untempered as loaded
   // multi-workgroup generation (k_mt_gen_multi): workgroup g starts at block g * bpg from
   // the jump polynomial jpoly[g] (z^(624 * bpg * g - 1) mod phi, 312 words each)
   const uint64_t* jpoly;

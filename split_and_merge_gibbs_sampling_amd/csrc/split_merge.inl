@@ -472,7 +472,7 @@ static int sm_chain(Ctx* c, SmWork& W, const std::vector<int>& S, HState& s, int
   c->rng_sync();
   const uint64_t P0 = c->rng.pos;
   RngWindow* Wn = c->window_at(P0, (int64_t)t * (nS + 2 * pf.need));
-  if (!Wn || !c->can_adopt(*Wn, P0)) return -1;
+  if (!Wn) return -1;
   SmTimer tm(c->stats.t_sm_scan_ms);
   c->dspec_drain();                                 // phd's scratch is the chain's now
   hipStream_t st = c->stream;
