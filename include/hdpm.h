@@ -507,6 +507,58 @@ int hdpm_trace_tables(hdpm_ctx* ctx, const int32_t* cls, int32_t ncand, int32_t 
 int hdpm_trace_distances(hdpm_ctx* ctx, const int32_t* cls, int32_t ncand, double* vi, uint64_t* binder,
                          int32_t* draw_k);
 int hdpm_trace_affinity(hdpm_ctx* ctx, const int32_t* cl, int32_t Ka, uint64_t* aff, uint64_t* cross);
+/* A point estimate refined by single-point moves (the local search of mcclust.ext's greedy and
+ * of SALSO, without their merges, splits and restarts), after hdpm_trace_build and with
+ * hdpm_trace_affinity's refusals; an unknown loss or a negative max_rounds is HDPM_E_ARG too.
+ * With n_a the class sizes of cl, T^m its table against draw z_m and
+ *   h(t) = (t + 1) log2(t + 1) - t log2 t, h(0) = 0, evaluated as
+ *          log2(t + 1) + t log1p(1 / t) / ln 2,
+ * moving point i alone from a = cl[i] to class b != a changes the loss by
+ *   HDPM_LOSS_VI:     gain[i][b] = (M (h(n_b) - h(n_a - 1))
+ *                                   - 2 sum_m (h(T^m[b][z_m(i)]) - h(T^m[a][z_m(i)] - 1))) / (M N),
+ *                     the change of hdpm_trace_losses' vi;
+ *   HDPM_LOSS_BINDER: gain[i][b] = M (n_b - n_a - 1) - 2 (aff[i][b] - aff[i][a]), the change of
+ *                     the integer M A + P - 2 Q (M times Binder's loss), exact: accumulated in
+ *                     64-bit integers and returned as a double that holds it (|gain| <= 3 M N),
+ * and gain[i][a] = 0.  Column b = Ka is a new class of its own (n_b = 0, T[b][.] = 0).  VI's sum
+ * over the draws is taken in draw order, per (point, class); no result depends on how the points
+ * are cut into blocks.
+ *
+ * hdpm_trace_move_gains: full[i * (Ka + 1) + b] = gain[i][b] (N x (Ka + 1); testing and
+ *   inspection), best[i] the class with the smallest gain and gain[i] that gain (N each, the
+ *   only bytes that leave the device without full).  The own class wins a tie, then the lowest
+ *   class.  The new class is offered only while Ka < 255: at Ka = 255 its column holds +inf and
+ *   is never best.  Any output may be NULL.  The gains are staged on the device in blocks of
+ *   points within table_budget_bytes (whole groups of 16 points, at least 16).
+ * hdpm_trace_refine: descends from cl (labels 0..254) by rounds of such moves.  One round on the
+ *   current partition c with loss L: the candidates are the points with gain < 0; of those whose
+ *   best is the new class only the one with the smallest gain stays (the lowest index breaking a
+ *   tie): at most one new class per round.  No candidate: stop, converged = 1 (c is a minimum
+ *   under single-point moves).  The candidates are ordered by (gain, index) ascending, k their
+ *   number.  Trial: the first k moves applied at once, the result relabelled 0..K-1 by first
+ *   appearance, its loss evaluated exactly as hdpm_trace_losses does (VI's double, Binder's
+ *   integer) and accepted iff strictly below L; a rejected trial with k = 1 stops the run with
+ *   converged = 1 (VI only, by rounding), any other is followed by k = ceil(k / 2).  After an
+ *   accepted trial the next round starts from the full candidate set; after max_rounds accepted
+ *   rounds the run stops with converged = 0 unless no candidate is left.  Simultaneous moves are
+ *   no descent by themselves; the strict test makes every accepted round one.
+ *   cl_out[N] is the end state (labels 0..K-1 by first appearance: the start relabelled if no
+ *   round was accepted); info->rounds the accepted rounds, trials the evaluated trials, moved
+ *   the moves of the accepted trials, K the end state's classes, start / value the loss before
+ *   and after; history[max_rounds + 1] (may be NULL) the loss at the start and after each
+ *   accepted round.  VI values are hdpm_trace_losses' vi; Binder values are the integer
+ *   M A + P - 2 Q as a double, and Binder needs N^2 M < 2^63 (HDPM_E_ARG otherwise). */
+#define HDPM_LOSS_VI 0
+#define HDPM_LOSS_BINDER 1
+typedef struct hdpm_refine_info {
+  int32_t rounds, trials, converged, K;
+  int64_t moved;
+  double start, value;
+} hdpm_refine_info;
+int hdpm_trace_move_gains(hdpm_ctx* ctx, const int32_t* cl, int32_t Ka, int32_t loss, int32_t* best, double* gain,
+                          double* full);
+int hdpm_trace_refine(hdpm_ctx* ctx, const int32_t* cl, int32_t loss, int32_t max_rounds, int32_t* cl_out,
+                      hdpm_refine_info* info, double* history);
 /* mcclust.ext minVI(method = "avg") / mcclust minbinder(method = "avgl") =
  * hclust(as.dist(1 - psm), "average") + cutree, from the saved labels alone.  Points whose
  * labels agree in every draw have psm = 1 (distance 0) and any other pair has distance

@@ -5,8 +5,8 @@ kernels and the host runtime live in ``libhdpm.so`` (C ABI: include/hdpm.h); thi
 package is the Python mirror of the reference interface.
 """
 from ._lib import HdpmError, build  # noqa: F401
-from .posterior import LabelTrace, Predictive, credible_ball, lpml, minbinder, waic  # noqa: F401
+from .posterior import LabelTrace, Predictive, credible_ball, lpml, minbinder, refine, waic  # noqa: F401
 from .sampler import Debug, Engine, run_markov_chain  # noqa: F401
 
 __all__ = ["Engine", "Debug", "run_markov_chain", "HdpmError", "build", "LabelTrace", "minbinder", "credible_ball",
-           "Predictive", "waic", "lpml"]
+           "Predictive", "waic", "lpml", "refine"]

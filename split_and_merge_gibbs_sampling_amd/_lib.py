@@ -32,6 +32,7 @@ EXPORTS = (
     "hdpm_trace_build", "hdpm_trace_terms", "hdpm_trace_losses", "hdpm_trace_tables",
     "hdpm_trace_groups", "hdpm_trace_group_info", "hdpm_trace_avg_tree", "hdpm_trace_cut_losses",
     "hdpm_trace_cut_labels", "hdpm_trace_distances", "hdpm_trace_affinity", "hdpm_sm_last_terms",
+    "hdpm_trace_move_gains", "hdpm_trace_refine",
     "hdpm_predict_build", "hdpm_predict_new", "hdpm_predict_own", "hdpm_predict_loglik",
     "hdpm_predict_partial", "hdpm_predict_impute",
     "hdpm_debug_launches",
@@ -145,6 +146,12 @@ class SmTerms(C.Structure):
                 "log_ratio": self.log_ratio, "log_u": self.log_u}
 
 
+class RefineInfo(C.Structure):
+    """hdpm_refine_info (include/hdpm.h)."""
+    _fields_ = [(n, C.c_int32) for n in ("rounds", "trials", "converged", "K")] + \
+        [("moved", C.c_int64), ("start", C.c_double), ("value", C.c_double)]
+
+
 class Launches(C.Structure):
     """hdpm_launches (include/hdpm.h): what the process's last launches used."""
     _fields_ = [(n, C.c_int32) for n in (
@@ -234,6 +241,8 @@ def lib():
         "hdpm_trace_cut_labels": ([vp, i32, vp], C.c_int),
         "hdpm_trace_distances": ([vp, vp, i32, vp, vp, vp], C.c_int),
         "hdpm_trace_affinity": ([vp, vp, i32, vp, vp], C.c_int),
+        "hdpm_trace_move_gains": ([vp, vp, i32, i32, vp, vp, vp], C.c_int),
+        "hdpm_trace_refine": ([vp, vp, i32, i32, vp, P(RefineInfo), vp], C.c_int),
         "hdpm_predict_build": ([vp, i32, vp, f64, vp, vp, vp], C.c_int),
         "hdpm_predict_new": ([vp, vp, i32, vp, i32, vp, vp, vp], C.c_int),
         "hdpm_predict_own": ([vp, vp, vp, vp, vp], C.c_int),

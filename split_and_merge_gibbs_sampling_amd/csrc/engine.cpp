@@ -5557,6 +5557,16 @@ int hdpm_trace_affinity(hdpm_ctx* h, const int32_t* cl, int32_t Ka, uint64_t* af
   CTX();
   GUARD(return ctx->sum.trace_affinity(cl, Ka, aff, cross);)
 }
+int hdpm_trace_move_gains(hdpm_ctx* h, const int32_t* cl, int32_t Ka, int32_t loss, int32_t* best, double* gain,
+                          double* full) {
+  CTX();
+  GUARD(return ctx->sum.trace_move_gains(cl, Ka, loss, best, gain, full);)
+}
+int hdpm_trace_refine(hdpm_ctx* h, const int32_t* cl, int32_t loss, int32_t max_rounds, int32_t* cl_out,
+                      hdpm_refine_info* info, double* history) {
+  CTX();
+  GUARD(return ctx->sum.trace_refine(cl, loss, max_rounds, cl_out, info, history);)
+}
 int hdpm_trace_groups(hdpm_ctx* h, int32_t max_groups, int32_t hash_bits, int32_t* U_out) {
   CTX();
   GUARD(return ctx->sum.trace_groups(max_groups, hash_bits, U_out);)

@@ -1,6 +1,7 @@
 // summary_host.cpp -- host side of the posterior summaries (summary_host.hpp): the dense
 // psm of posterior.hip, the matrix-free summaries of trace_summary.hip, the uncertainty
-// calls of trace_uncertainty.hip, the average-linkage search of trace_tree.hpp and the
+// calls of trace_uncertainty.hip, the single-point moves of trace_refine.hip (their descent
+// rule is in trace_refine.hpp), the average-linkage search of trace_tree.hpp and the
 // posterior predictive of predict.hip.  The arithmetic that turns the device's integer sums
 // into losses is in trace_loss.hpp, that of the predictive's tables and checks in
 // predict_host.hpp.
@@ -15,6 +16,7 @@
 #include "predict_host.hpp"
 #include "summary_launch.hpp"
 #include "trace_loss.hpp"
+#include "trace_refine.hpp"
 #include "trace_tree.hpp"
 
 namespace hdpm {
@@ -402,6 +404,100 @@ int Summaries::trace_affinity(const int32_t* cl, int32_t Ka, uint64_t* aff, uint
     }
     HIPCHK(hipStreamSynchronize(stream));
   });
+  return HDPM_OK;
+}
+
+// ---- a point estimate refined by single-point moves (trace_refine.hip, trace_refine.hpp)
+// cl checked, labels 0..Ka-1: the tables of the one candidate, their transposed form for the
+// loss, then blocks of points: sums, gains and argmin on the device, best / gain (and the
+// full rows on request) to the caller as each block completes
+void Summaries::move_gains(const int32_t* cl, int Ka, int loss, int32_t* best, double* gain, double* full) {
+  const int N = tr_N, Np = tr_Np, M = tr_M, Kz = tr_Kz, L = Ka + 1;
+  blocks({cl, 0, 1}, Ka, false, false, false, [&](int, int, const uint8_t* rows) {
+    const size_t per = (size_t)M * Ka * Kz;
+    std::vector<uint64_t> sz((size_t)L, 0);
+    for (int i = 0; i < N; ++i) sz[rows[i]]++;
+    std::vector<double> ct((size_t)L + Ka, 0.0);
+    for (int b = 0; b < L; ++b) ct[b] = loss == HDPM_LOSS_VI ? rf_h((double)sz[b]) : (double)sz[b];
+    if (loss == HDPM_LOSS_VI)
+      for (int a = 0; a < Ka; ++a) ct[L + a] = sz[a] > 0 ? rf_h((double)(sz[a] - 1)) : 0.0;
+    d_rf_ct.ensure(ct.size());
+    HIPCHK(hipMemcpyAsync(d_rf_ct.p, ct.data(), ct.size() * 8, hipMemcpyHostToDevice, stream));
+    const void* tabT;
+    if (loss == HDPM_LOSS_VI) {
+      d_rf_h.ensure(per * 2);
+      HIPCHK(launch_rf_htable(d_tr_tab.p, M, Ka, Kz, d_rf_h.p, stream));
+      tabT = d_rf_h.p;
+    } else {
+      d_tr_tabT.ensure(per);
+      HIPCHK(launch_tr_transpose(d_tr_tab.p, M, Ka, Kz, d_tr_tabT.p, stream));
+      tabT = d_tr_tabT.p;
+    }
+    // blocks of points: the staging (pb x (Ka + 1) x 8 bytes) within the table budget, in
+    // whole groups of 16 points and at least one (trace_affinity's rule)
+    size_t pb = (tr_budget / ((size_t)L * 8)) & ~(size_t)15;
+    pb = std::min(std::max<size_t>(pb, 16), (size_t)Np);
+    d_rf_stage.ensure(pb * L);
+    d_rf_best.ensure(pb);
+    d_rf_gain.ensure(pb);
+    for (int64_t i0 = 0; i0 < N; i0 += (int64_t)pb) {
+      const int np = (int)std::min<int64_t>((int64_t)pb, N - i0);
+      HIPCHK(launch_rf_gains(loss, d_tr_lab.p, d_tr_cls.p, Np, M, Ka, Kz, tabT, (int)i0, np, d_rf_ct.p, N,
+                             full ? 1 : 0, d_rf_stage.p, d_rf_best.p, d_rf_gain.p, stream));
+      if (best) HIPCHK(hipMemcpyAsync(best + i0, d_rf_best.p, (size_t)np * 4, hipMemcpyDeviceToHost, stream));
+      if (gain) HIPCHK(hipMemcpyAsync(gain + i0, d_rf_gain.p, (size_t)np * 8, hipMemcpyDeviceToHost, stream));
+      if (full)
+        HIPCHK(hipMemcpyAsync(full + (size_t)i0 * L, d_rf_stage.p, (size_t)np * L * 8, hipMemcpyDeviceToHost, stream));
+      HIPCHK(hipStreamSynchronize(stream));
+    }
+  });
+}
+int Summaries::trace_move_gains(const int32_t* cl, int32_t Ka, int32_t loss, int32_t* best, double* gain,
+                                double* full) {
+  int used = 0;   // the largest label + 1
+  if (int st = check(cl, 1, &used)) return st;
+  if (Ka < 1 || Ka > 255) { err = "trace: Ka must be in 1..255"; return HDPM_E_ARG; }
+  if (used > Ka) { err = "trace: the partition's labels must be in 0..Ka-1"; return HDPM_E_ARG; }
+  if (loss != HDPM_LOSS_VI && loss != HDPM_LOSS_BINDER) { err = "trace: unknown loss"; return HDPM_E_ARG; }
+  if (best || gain || full) move_gains(cl, Ka, loss, best, gain, full);
+  return HDPM_OK;
+}
+int Summaries::trace_refine(const int32_t* cl, int32_t loss, int32_t max_rounds, int32_t* cl_out,
+                            hdpm_refine_info* info, double* history) {
+  int used = 0;
+  if (int st = check(cl, 1, &used)) return st;
+  if (loss != HDPM_LOSS_VI && loss != HDPM_LOSS_BINDER) { err = "trace: unknown loss"; return HDPM_E_ARG; }
+  if (max_rounds < 0 || !cl_out) { err = "trace: refine needs max_rounds >= 0 and cl_out"; return HDPM_E_ARG; }
+  if (loss == HDPM_LOSS_BINDER && !tl_fits63((uint64_t)tr_N, (uint64_t)tr_M)) {
+    err = "trace: N^2 M does not fit 63 bits: Binder's integer would overflow";
+    return HDPM_E_ARG;
+  }
+  auto gains = [&](const int32_t* c, int K, int32_t* best, double* gain) {
+    move_gains(c, K, loss, best, gain, nullptr);
+  };
+  RfInfo r;
+  if (loss == HDPM_LOSS_VI) {
+    rf_run<double>(cl, tr_N, max_rounds, gains, [&](const int32_t* c, int K) {
+      double v = 0.0;
+      losses({c, 0, 1}, K, nullptr, &v, nullptr, nullptr);
+      return v;
+    }, cl_out, &r, history);
+  } else {
+    rf_run<uint64_t>(cl, tr_N, max_rounds, gains, [&](const int32_t* c, int K) {
+      uint64_t A = 0, Q = 0;
+      losses({c, 0, 1}, K, nullptr, nullptr, &A, &Q);
+      return (uint64_t)tr_M * A + tr_P - 2 * Q;
+    }, cl_out, &r, history);
+  }
+  if (info) {
+    info->rounds = r.rounds;
+    info->trials = r.trials;
+    info->converged = r.converged;
+    info->K = r.K;
+    info->moved = r.moved;
+    info->start = r.start;
+    info->value = r.value;
+  }
   return HDPM_OK;
 }
 

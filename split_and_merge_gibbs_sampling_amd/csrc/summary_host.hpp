@@ -13,6 +13,8 @@
 
 #include "host_util.hpp"
 
+struct hdpm_refine_info;
+
 namespace hdpm {
 
 class Summaries {
@@ -30,6 +32,9 @@ class Summaries {
   int trace_tables(const int32_t* cls, int32_t ncand, int32_t m0, int32_t nm, uint32_t* out);
   int trace_distances(const int32_t* cls, int32_t ncand, double* vi, uint64_t* binder, int32_t* draw_k);
   int trace_affinity(const int32_t* cl, int32_t Ka, uint64_t* aff, uint64_t* cross);
+  int trace_move_gains(const int32_t* cl, int32_t Ka, int32_t loss, int32_t* best, double* gain, double* full);
+  int trace_refine(const int32_t* cl, int32_t loss, int32_t max_rounds, int32_t* cl_out, hdpm_refine_info* info,
+                   double* history);
   int trace_groups(int32_t max_groups, int32_t hash_bits, int32_t* U_out);
   int trace_group_info(int32_t* first, int32_t* weight, int32_t* group_of, uint32_t* counts);
   int trace_avg_tree(int32_t* merge, double* height);
@@ -74,6 +79,11 @@ class Summaries {
   std::vector<int32_t> tr_Km;
   DevBuf<uint32_t> d_tr_tabT;
   DevBuf<uint64_t> d_tr_aff, d_tr_cross;
+  // the single-point moves (trace_refine.hip): the (h(T), h(T - 1)) pairs of the transposed
+  // tables, the class table, and per block of points the staged sums, best and gain
+  DevBuf<double> d_rf_h, d_rf_ct, d_rf_gain;
+  DevBuf<uint64_t> d_rf_stage;
+  DevBuf<int32_t> d_rf_best;
   // groups of equal label columns and their average-linkage tree (trace_groups ..
   // trace_cut_labels): the open-addressing table, group_of per point, the groups'
   // signatures both ways round, S (U x U) once it is first needed, the tree on the host
@@ -117,6 +127,7 @@ class Summaries {
   template <class F>
   void blocks(Cands cd, int Ka, bool terms, bool want_all, bool reduce, F f);
   void losses(Cands cd, int Ka, double* vi_lb, double* vi, uint64_t* binder_A, uint64_t* binder_Q);
+  void move_gains(const int32_t* cl, int Ka, int loss, int32_t* best, double* gain, double* full);
   void group_counts();
 };
 

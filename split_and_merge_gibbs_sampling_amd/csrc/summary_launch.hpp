@@ -1,7 +1,8 @@
 // summary_launch.hpp -- launchers of the posterior-summary kernels: posterior.hip
 // (launch_psm, launch_vi_terms), trace_summary.hip (launch_tr_pack .. launch_tr_reduce,
 // launch_tg_*) and trace_uncertainty.hip (launch_tr_transpose, launch_tr_affinity,
-// launch_tr_cross) and predict.hip (launch_pr_new .. launch_pr_impute).  Included by the units that
+// launch_tr_cross), trace_refine.hip (launch_rf_htable, launch_rf_gains) and predict.hip
+// (launch_pr_new .. launch_pr_impute).  Included by the units that
 // define them and by summary_host.cpp, their only caller.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -26,6 +27,13 @@ hipError_t launch_tr_transpose(const uint32_t* tab, int M, int Ka, int Kz, uint3
 hipError_t launch_tr_affinity(const uint8_t* lab, int Np, int M, int Ka, int Kz, const uint32_t* tabT, int i0, int npts,
                               uint64_t* out, hipStream_t s);
 hipError_t launch_tr_cross(const uint32_t* tabT, int M, int Ka, int Kz, uint64_t* cross, hipStream_t s);
+// trace_refine.hip.  launch_rf_gains: the staged sums of npts points from i0, then their gains
+// (over the sums, if full) and argmin; tabT is launch_rf_htable's array for HDPM_LOSS_VI and
+// launch_tr_transpose's for HDPM_LOSS_BINDER, ct the class table k_rf_best describes.
+hipError_t launch_rf_htable(const uint32_t* tab, int M, int Ka, int Kz, double* tabH, hipStream_t s);
+hipError_t launch_rf_gains(int loss, const uint8_t* lab, const uint8_t* cls, int Np, int M, int Ka, int Kz,
+                           const void* tabT, int i0, int npts, const double* ct, int N, int full, uint64_t* stage,
+                           int32_t* best, double* gain, hipStream_t s);
 hipError_t launch_tg_insert(const uint8_t* lab, int N, int Np, int M, int hash_bits, uint32_t tslots,
                             uint32_t max_groups, uint32_t* rep, uint32_t* first, uint32_t* pslot, uint32_t* ctl,
                             hipStream_t s);

@@ -18,7 +18,9 @@ default search -- the cuts of the average-linkage tree -- on the groups of point
 labels agree in every draw, again with no matrix.  ``credible_ball`` (mcclust.ext
 ``credibleball``) and ``LabelTrace.membership`` / ``cluster_similarity`` (the content of the
 script's PSM plot ordered by ``VI$cl``) say how far that estimate can be trusted, from the
-same tables (csrc/trace_uncertainty.hip).  ``Predictive`` reads the recorded centers and
+same tables (csrc/trace_uncertainty.hip), and ``refine`` improves it by single-point moves on
+the expected VI or Binder's loss until no move helps (csrc/trace_refine.hip;
+``LabelTrace.move_gains`` gives every point's best move).  ``Predictive`` reads the recorded centers and
 sigmas beside the labels (csrc/predict.hip through ``hdpm_predict_*``): the posterior
 predictive of rows the chain never saw -- their density, their class of a point estimate, the
 probability of a cluster of their own -- and the pointwise log-likelihood of the training rows
@@ -271,6 +273,31 @@ class LabelTrace:
                     out[a, a] = (x[a][a] - self.M * n[a]) / (self.M * n[a] * (n[a] - 1))
         return out
 
+    # ---- single-point moves (csrc/trace_refine.hip)
+
+    def move_gains(self, cl, loss: str = "VI", full: bool = False, Ka: int | None = None):
+        """(best, gain[, gains]): what moving each point alone to another class of ``cl``
+        (relabelled 0..Ka-1 as the candidates are; with ``Ka`` given, labels 0..Ka-1 as they
+        stand, so a class may be empty) would change in ``loss``: "VI", the change of ``vi``, or
+        "Binder", the change of the exact integer M A + P - 2 Q (M times ``binder``), as a
+        double that holds it.  gains is N x (Ka + 1), column Ka a new class of its own (+inf at
+        Ka = 255) and the own class 0; best[i] is the class with the smallest gain (the own
+        class wins a tie, then the lowest class) and gain[i] that gain.  Only best and gain
+        leave the device unless ``full``."""
+        code = _loss_code(loss)
+        if Ka is None:
+            c = self._one(cl)[0]
+            Ka = int(c.max()) + 1
+        else:
+            c = np.ascontiguousarray(cl, dtype=np.int32).ravel()
+            if c.size != self.N:
+                raise ValueError("the partition must have N labels")
+        best, gain = np.zeros(self.N, np.int32), np.zeros(self.N)
+        gains = np.zeros((self.N, max(int(Ka), 0) + 1)) if full else None
+        self.eng._check(self.eng._L.hdpm_trace_move_gains(self.eng._h, ptr(c), int(Ka), code, ptr(best), ptr(gain),
+                                                          ptr(gains)))
+        return (best, gain, gains) if full else (best, gain)
+
     # ---- the average-linkage tree without the matrix (hdpm_trace_groups .. _cut_labels)
 
     def groups(self, max_groups: int = 8192, hash_bits: int = 0) -> dict:
@@ -496,6 +523,52 @@ def minbinder_avg(trace: LabelTrace, max_k: int | None = None, max_groups: int |
     num = [trace.M * a + P - 2 * q for a, q in zip(A, Q)]
     best = min(range(len(num)), key=num.__getitem__)
     return trace.cut(best + 1) + 1, float(A[best] + (P - 2 * Q[best]) / trace.M)
+
+
+def _loss_code(loss: str) -> int:
+    if loss not in ("VI", "Binder"):
+        raise ValueError(f"unknown loss {loss!r}")
+    return 0 if loss == "VI" else 1       # HDPM_LOSS_VI, HDPM_LOSS_BINDER
+
+
+def refine(trace: LabelTrace, cl, loss: str = "VI", max_rounds: int = 100) -> dict:
+    """A point estimate improved by single-point moves (the local search of mcclust.ext's
+    ``greedy`` and of SALSO, without their merges, splits and restarts), with no N x N
+    matrix and no limit on the number of distinct label columns.  Each round takes every
+    point's best move from ``LabelTrace.move_gains``, at most one new class among them, and
+    applies the moves together, halving their number until the loss itself (``vi``, or
+    Binder's exact integer) falls strictly; include/hdpm.h states the rule.  It ends at a
+    partition that no single move improves (``converged``) or after ``max_rounds`` rounds.
+
+    Returns {"cl" (1-based, labelled by first appearance), "value", "start", "rounds",
+    "trials", "moved", "converged", "history"}: history holds the loss at the start and after
+    each accepted round.  For "Binder" value and start are ``LabelTrace.binder``'s values, which
+    history begins and ends with; between them it holds the integers M A + P - 2 Q divided by
+    M (the same numbers, rounded once instead of twice).  All are combined as Python ints."""
+    if not isinstance(trace, LabelTrace):
+        raise ValueError("refine needs a LabelTrace")
+    code = _loss_code(loss)
+    if max_rounds < 0:
+        raise ValueError("max_rounds must be at least 0")
+    c = trace._one(cl)[0]
+    out = np.zeros(trace.N, np.int32)
+    info = _lib.RefineInfo()
+    hist = np.zeros(int(max_rounds) + 1)
+    eng = trace.eng
+    eng._check(eng._L.hdpm_trace_refine(eng._h, ptr(c), code, int(max_rounds), ptr(out), C.byref(info), ptr(hist)))
+    hist = hist[:info.rounds + 1]
+    start, value = float(info.start), float(info.value)
+    if loss == "Binder":
+        # the value of LabelTrace.binder, A + (P - 2 Q) / M, with P - 2 Q = (M A + P - 2 Q) - M A
+        def binder(num, labels):
+            n = np.bincount(labels).tolist()
+            A = sum(x * (x - 1) // 2 for x in n)
+            return float(A + (int(num) - trace.M * A) / trace.M)
+        start, value = binder(info.start, c), binder(info.value, out)
+        hist = np.array([int(x) / trace.M for x in hist])
+        hist[0], hist[-1] = start, value if info.rounds else start
+    return {"cl": out + 1, "value": value, "start": start, "rounds": int(info.rounds), "trials": int(info.trials),
+            "moved": int(info.moved), "converged": bool(info.converged), "history": hist}
 
 
 def comp_psm(c_trace, device: int = 0) -> np.ndarray:
