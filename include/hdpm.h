@@ -623,7 +623,7 @@ int hdpm_trace_cut_labels(hdpm_ctx* ctx, int32_t k, int32_t* cl);
  *
  * hdpm_predict_build: the parameters of the M draws, total_cls[M] and sum_s K_s rows of d
  *   centers and sigmas in saved-iteration order (what hdpm_record_take returns), kept on the
- *   device as a byte and dhamming's (match, mismatch) pair per (s, k, j).
+ *   device as a byte, dhamming's (match, mismatch) pair and the raw sigma per (s, k, j).
  * hdpm_predict_new: ny rows codes[ny x d].  lpd[y] = log((1/M) sum_s exp(lse^s)) - log(N + gamma),
  *   the log posterior predictive density; p_new[y] = (1/M) sum_s r^s_0, the probability of a
  *   cluster of its own; with a partition cl[N] of the training points into classes 0..Ka-1
@@ -683,6 +683,38 @@ int hdpm_predict_partial(hdpm_ctx* ctx, const uint8_t* codes, int32_t ny, const 
                          double* p_new, double* coclass);
 int hdpm_predict_impute(hdpm_ctx* ctx, const uint8_t* codes, int32_t ny, int64_t n_missing, int32_t ld, double* pmf,
                         double* lpd);
+/* What each class of a point estimate is: the center code of every attribute with its posterior
+ * probability, and the sigma of every attribute with its spread.  After hdpm_trace_build and
+ * hdpm_predict_build; cl[N] holds labels 0..Ka-1, 1 <= Ka <= 255, a class may be empty
+ * (hdpm_predict_new's rules for cl).  For a point i of class a, draw s says "your center is
+ * c^s_{z_s(i)}, your sigma is sg^s_{z_s(i)}"; averaged over the members of a and over the draws
+ * this does not depend on how a draw numbers its clusters, so no labels are matched between
+ * draws, and the member sums are sums over the contingency table T^s[a][k] of cl against draw s.
+ * With n_a the class sizes, c_kj / sg_kj draw s's parameters and em_kj = exp(match_kj), ei_kj =
+ * exp(mismatch_kj) (hdpm_predict_impute's values):
+ *   center_cnt[(a * d + j) * ld + l - 1] = sum_s sum_k T^s[a][k] [c^s_kj == l], an exact integer;
+ *     divided by M n_a it is the posterior probability that the center of a member of a has code
+ *     l at attribute j.  Slots m_j .. ld-1 are 0.
+ *   sigma_trace[(s * Ka + a) * d + j] = u_s = (sum_k (double)T^s[a][k] * sg^s_kj) / (double)n_a,
+ *     k in cluster order, plain multiply and add: the relabelled parameter trace (M x Ka x d).
+ *   sigma_mean, sigma_var (Ka x d): Welford's recurrence over u_s in draw order from mean = 0,
+ *     m2 = 0: delta = u - mean; mean = mean + delta / (s + 1); m2 = m2 + delta * (u - mean);
+ *     sigma_mean is the final mean and sigma_var = m2 / (M - 1), 0.0 when M = 1 (the variance,
+ *     not the sd: no device sqrt).
+ *   code_pmf[(a * d + j) * ld + l - 1] = (1 / (M n_a)) sum_s sum_k T^s[a][k] (l == c^s_kj ?
+ *     em_kj : ei_kj), the model's predictive law of the code of a member of a at attribute j, to
+ *     hold against the class's observed code frequencies; slots m_j .. ld-1 are 0.0.  The sums
+ *     run over s in draw order, then k in cluster order; the device keeps base = sum T ei and
+ *     per level sum_{c = l} T (em - ei) and returns (base + that) / (M n_a), so the value is
+ *     within rounding of the definition (M K terms in (0, 1]), not its bits.
+ * An empty class gets 0 / 0.0 in every output.  Any output may be NULL and a call computes only
+ * what its outputs need.  The level rows are staged in blocks of attributes and sigma_trace in
+ * chunks of draws that obey table_budget_bytes (at least one attribute, one draw), each copied
+ * out as it completes; no result depends on the budget, bit for bit.  HDPM_E_ARG with a message
+ * for: a call before either build; a label >= Ka, or Ka outside 1..255; ld outside 1..255 or
+ * below the largest m_j (the attribute is named). */
+int hdpm_predict_profile(hdpm_ctx* ctx, const int32_t* cl, int32_t Ka, int32_t ld, uint64_t* center_cnt,
+                         double* code_pmf, double* sigma_mean, double* sigma_var, double* sigma_trace);
 /* Testing: one draw on the device from log-weights logw[E] (E <= 256) and the uniform rU --
  * the n8:95-102 categorical draw (two_way = 0; *pick = the 0-based index, or -status) or the
  * sm:204-215 two-way draw (two_way = 1, E = 2) -- with the engine's exp, glibc's algorithm

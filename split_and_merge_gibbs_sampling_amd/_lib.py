@@ -34,7 +34,7 @@ EXPORTS = (
     "hdpm_trace_cut_labels", "hdpm_trace_distances", "hdpm_trace_affinity", "hdpm_sm_last_terms",
     "hdpm_trace_move_gains", "hdpm_trace_refine",
     "hdpm_predict_build", "hdpm_predict_new", "hdpm_predict_own", "hdpm_predict_loglik",
-    "hdpm_predict_partial", "hdpm_predict_impute",
+    "hdpm_predict_partial", "hdpm_predict_impute", "hdpm_predict_profile",
     "hdpm_debug_launches",
 )
 
@@ -249,6 +249,7 @@ def lib():
         "hdpm_predict_loglik": ([vp, i32, vp, i32, vp, vp], C.c_int),
         "hdpm_predict_partial": ([vp, vp, i32, vp, i32, vp, vp, vp], C.c_int),
         "hdpm_predict_impute": ([vp, vp, i32, i64, i32, vp, vp], C.c_int),
+        "hdpm_predict_profile": ([vp, vp, i32, i32, vp, vp, vp, vp, vp], C.c_int),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name)

@@ -5616,6 +5616,11 @@ int hdpm_predict_impute(hdpm_ctx* h, const uint8_t* codes, int32_t ny, int64_t n
   CTX();
   GUARD(return ctx->sum.predict_impute(codes, ny, n_missing, ld, pmf, lpd);)
 }
+int hdpm_predict_profile(hdpm_ctx* h, const int32_t* cl, int32_t Ka, int32_t ld, uint64_t* center_cnt,
+                         double* code_pmf, double* sigma_mean, double* sigma_var, double* sigma_trace) {
+  CTX();
+  GUARD(return ctx->sum.predict_profile(cl, Ka, ld, center_cnt, code_pmf, sigma_mean, sigma_var, sigma_trace);)
+}
 int hdpm_debug_draw(hdpm_ctx* h, const double* logw, int32_t E, double rU, int32_t two_way, int32_t ocml,
                     int32_t* pick) {
   CTX();

@@ -2,9 +2,10 @@
 // psm of posterior.hip, the matrix-free summaries of trace_summary.hip, the uncertainty
 // calls of trace_uncertainty.hip, the single-point moves of trace_refine.hip (their descent
 // rule is in trace_refine.hpp), the average-linkage search of trace_tree.hpp and the
-// posterior predictive of predict.hip.  The arithmetic that turns the device's integer sums
-// into losses is in trace_loss.hpp, that of the predictive's tables and checks in
-// predict_host.hpp.
+// posterior predictive of predict.hip with the class profiles of profile.hip.  The arithmetic
+// that turns the device's integer sums into losses is in trace_loss.hpp, that of the
+// predictive's tables and checks in predict_host.hpp, the profiles' checks and cuts in
+// profile_host.hpp.
 #include "summary_host.hpp"
 
 #include <algorithm>
@@ -14,6 +15,7 @@
 
 #include "../../include/hdpm.h"
 #include "predict_host.hpp"
+#include "profile_host.hpp"
 #include "summary_launch.hpp"
 #include "trace_loss.hpp"
 #include "trace_refine.hpp"
@@ -676,6 +678,8 @@ int Summaries::predict_build(int32_t d, const int32_t* attrisize, double gamma, 
   d_pr_mm.ensure(mm.size());
   d_pr_lognk.ensure(lognk.size());
   d_pr_off.ensure(pr_off.size());
+  d_pr_sig.ensure((size_t)rows * d);
+  HIPCHK(hipMemcpyAsync(d_pr_sig.p, sigmas, (size_t)rows * d * 8, hipMemcpyHostToDevice, stream));
   HIPCHK(hipMemcpyAsync(d_pr_cen.p, cen.data(), cen.size(), hipMemcpyHostToDevice, stream));
   HIPCHK(hipMemcpyAsync(d_pr_mm.p, mm.data(), mm.size() * 8, hipMemcpyHostToDevice, stream));
   HIPCHK(hipMemcpyAsync(d_pr_lognk.p, lognk.data(), lognk.size() * 8, hipMemcpyHostToDevice, stream));
@@ -794,6 +798,19 @@ void Summaries::predict_blocks(const uint8_t* codes, int64_t ny, int s0, int s1,
   }
 }
 
+// the exps of the (match, mismatch) pairs and attrisize on the device, built at the first call
+// after predict_build that reads them (imputation, the profiles' code law)
+void Summaries::need_emm() {
+  if (pr_emm) return;
+  const size_t n = (size_t)pr_off[tr_M] * pr_d * 2;
+  d_pr_emm.ensure(n);
+  d_pr_att.ensure((size_t)pr_d);
+  HIPCHK(launch_pr_exp(d_pr_mm.p, (int64_t)n, d_pr_emm.p, stream));
+  HIPCHK(hipMemcpyAsync(d_pr_att.p, pr_att.data(), (size_t)pr_d * 4, hipMemcpyHostToDevice, stream));
+  HIPCHK(hipStreamSynchronize(stream));
+  pr_emm = true;
+}
+
 // Imputation: blocks of rows (whole quanta of 64) and, within a block, chunks of draws, cut so
 // that the block's staging -- packed codes, scratch columns, carried sums, the entries' list,
 // pmf rows and carried sums, and the rows' records of one chunk of draws -- obeys the table
@@ -804,15 +821,7 @@ void Summaries::predict_blocks(const uint8_t* codes, int64_t ny, int s0, int s1,
 void Summaries::impute_blocks(const uint8_t* codes, int64_t ny, int ld, double* pmf, double* lpd) {
   const int d = pr_d, M = tr_M;
   const size_t q = kPrRowQuantum, nw = (size_t)pr_d4(d) / 4;
-  if (!pr_emm) {
-    const size_t n = (size_t)pr_off[M] * d * 2;
-    d_pr_emm.ensure(n);
-    d_pr_att.ensure((size_t)d);
-    HIPCHK(launch_pr_exp(d_pr_mm.p, (int64_t)n, d_pr_emm.p, stream));
-    HIPCHK(hipMemcpyAsync(d_pr_att.p, pr_att.data(), (size_t)d * 4, hipMemcpyHostToDevice, stream));
-    HIPCHK(hipStreamSynchronize(stream));
-    pr_emm = true;
-  }
+  need_emm();
   const size_t rec1 = (size_t)pr_Kmax + 2;                    // the longest record of one draw
   const size_t row_bytes = nw * 4 + ((size_t)pr_Kmax + 1) * 8 + 16 + 8 + 24 + rec1 * 8;
   const size_t entry_bytes = (size_t)ld * 8 + 24;
@@ -1019,6 +1028,78 @@ int Summaries::predict_impute(const uint8_t* codes, int32_t ny, int64_t n_missin
   if (have == 0 && !lpd) return HDPM_OK;
   if (have == 0) predict_blocks(codes, ny, 0, tr_M, nullptr, 0, lpd, nullptr, nullptr, nullptr, nullptr, true);
   else impute_blocks(codes, ny, ld, pmf, lpd);
+  return HDPM_OK;
+}
+
+// ---- what each class of an estimate is (profile.hip, profile_host.hpp): the tables of the one
+// candidate stay on the device while the draws go through in chunks (u_s, then Welford's sums)
+// and the attributes in blocks (the level rows), each copied to the caller as it completes
+int Summaries::predict_profile(const int32_t* cl, int32_t Ka, int32_t ld, uint64_t* center_cnt, double* code_pmf,
+                               double* sigma_mean, double* sigma_var, double* sigma_trace) {
+  if (int st = need(false, false)) return st;
+  if (pr_d == 0) { err = "profile: hdpm_predict_build has not been called"; return HDPM_E_ARG; }
+  if (!cl) { err = "profile: no partition"; return HDPM_E_ARG; }
+  err = pr_check_classes(cl, tr_N, Ka);
+  if (!err.empty()) return HDPM_E_ARG;
+  err = pf_check_ld(pr_d, pr_att.data(), ld);
+  if (!err.empty()) return HDPM_E_ARG;
+  const bool sig = sigma_mean || sigma_var || sigma_trace, lev = center_cnt || code_pmf;
+  if (!sig && !lev) return HDPM_OK;
+  const int d = pr_d, M = tr_M, Kz = tr_Kz;
+  std::vector<double> na((size_t)Ka, 0.0);
+  for (int i = 0; i < tr_N; ++i) na[cl[i]] += 1.0;
+  d_pr_na.ensure((size_t)Ka);
+  HIPCHK(hipMemcpyAsync(d_pr_na.p, na.data(), (size_t)Ka * 8, hipMemcpyHostToDevice, stream));
+  if (code_pmf) need_emm();
+  blocks({cl, 0, 1}, Ka, false, false, false, [&](int, int, const uint8_t*) {
+    if (sig) {
+      const size_t n = (size_t)Ka * d;
+      const std::vector<int> cut = pf_draw_chunks(tr_budget, Ka, d, M);
+      size_t most = 0;
+      for (size_t c = 0; c + 1 < cut.size(); ++c) most = std::max(most, (size_t)(cut[c + 1] - cut[c]));
+      d_pf_u.ensure(most * n);
+      d_pf_st.ensure(4 * n);                          // (mean, m2) carried, then mean and var
+      for (size_t c = 0; c + 1 < cut.size(); ++c) {
+        const int s0 = cut[c], s1 = cut[c + 1];
+        HIPCHK(launch_pf_sigma({d_tr_tab.p, Ka, Kz, d, s0, s1, d_pr_off.p, d_pr_sig.p, d_pr_na.p, d_pf_u.p}, stream));
+        if (sigma_mean || sigma_var)
+          HIPCHK(launch_pf_welford({d_pf_u.p, (int)n, s0, s1, M, d_pf_st.p, d_pf_st.p + 2 * n, d_pf_st.p + 3 * n},
+                                   stream));
+        if (sigma_trace)
+          HIPCHK(hipMemcpyAsync(sigma_trace + (size_t)s0 * n, d_pf_u.p, (size_t)(s1 - s0) * n * 8,
+                                hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));         // the staging is reused by the next chunk
+      }
+      if (sigma_mean) HIPCHK(hipMemcpyAsync(sigma_mean, d_pf_st.p + 2 * n, n * 8, hipMemcpyDeviceToHost, stream));
+      if (sigma_var) HIPCHK(hipMemcpyAsync(sigma_var, d_pf_st.p + 3 * n, n * 8, hipMemcpyDeviceToHost, stream));
+      HIPCHK(hipStreamSynchronize(stream));
+    }
+    if (lev) {
+      const int slot_bytes = (center_cnt ? 8 : 0) + (code_pmf ? 8 : 0);
+      const std::vector<int> cut = pf_attr_blocks(tr_budget, Ka, ld, slot_bytes, d);
+      size_t most = 0;
+      for (size_t c = 0; c + 1 < cut.size(); ++c) most = std::max(most, (size_t)(cut[c + 1] - cut[c]));
+      const size_t cap = (size_t)Ka * most * ld;
+      if (center_cnt) d_pf_cnt.ensure(cap);
+      if (code_pmf) d_pf_law.ensure(cap);
+      for (size_t c = 0; c + 1 < cut.size(); ++c) {
+        const int j0 = cut[c], jb = cut[c + 1] - cut[c];
+        const size_t row = (size_t)jb * ld * 8;
+        HIPCHK(launch_pf_levels({d_tr_tab.p, M, Ka, Kz, d, j0, jb, ld, 0, d_pr_off.p, d_pr_cen.p, d_pr_emm.p,
+                                 d_pr_att.p, d_pr_na.p, center_cnt ? d_pf_cnt.p : nullptr,
+                                 code_pmf ? d_pf_law.p : nullptr},
+                                stream));
+        // class a's rows of the block are contiguous on both sides: Ka pieces of jb x ld slots
+        if (center_cnt)
+          HIPCHK(hipMemcpy2DAsync(center_cnt + (size_t)j0 * ld, (size_t)d * ld * 8, d_pf_cnt.p, row, row, (size_t)Ka,
+                                  hipMemcpyDeviceToHost, stream));
+        if (code_pmf)
+          HIPCHK(hipMemcpy2DAsync(code_pmf + (size_t)j0 * ld, (size_t)d * ld * 8, d_pf_law.p, row, row, (size_t)Ka,
+                                  hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));         // the staging is reused by the next block
+      }
+    }
+  });
   return HDPM_OK;
 }
 

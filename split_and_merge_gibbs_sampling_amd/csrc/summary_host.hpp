@@ -1,6 +1,6 @@
 // summary_host.hpp -- the posterior summaries of a context: the state and host logic behind
 // hdpm_psm_* (posterior.hip), hdpm_trace_* (trace_summary.hip, trace_uncertainty.hip) and
-// hdpm_predict_* (predict.hip).
+// hdpm_predict_* (predict.hip, profile.hip).
 //
 // The summaries work on saved labels and never touch chain state: of their context they use
 // the main stream and the error string, bound at construction.  Every method is the body of
@@ -50,6 +50,8 @@ class Summaries {
   int predict_partial(const uint8_t* codes, int32_t ny, const int32_t* cl, int32_t Ka, double* lpd, double* p_new,
                       double* coclass);
   int predict_impute(const uint8_t* codes, int32_t ny, int64_t n_missing, int32_t ld, double* pmf, double* lpd);
+  int predict_profile(const int32_t* cl, int32_t Ka, int32_t ld, uint64_t* center_cnt, double* code_pmf,
+                      double* sigma_mean, double* sigma_var, double* sigma_trace);
 
  private:
   hipStream_t& stream;
@@ -116,8 +118,14 @@ class Summaries {
   DevBuf<uint32_t> d_pr_ent;
   DevBuf<int32_t> d_pr_att;
   bool pr_emm = false;
+  // The profiles of an estimate's classes (profile.hip) add the raw sigmas (rows of d, as the
+  // pairs) and, per chunk of draws, u_s with the carried (mean, m2) and the final mean and var;
+  // per block of attributes, the level rows of the counts and of the code law
+  DevBuf<double> d_pr_sig, d_pf_u, d_pf_st, d_pf_law;
+  DevBuf<uint64_t> d_pf_cnt;
 
   struct Cands;
+  void need_emm();
   int need_predict(const uint8_t* codes, int64_t rows, bool partial = false);
   void predict_blocks(const uint8_t* codes, int64_t ny, int s0, int s1, const uint32_t* tab, int Ka, double* lpd,
                       double* p_new, double* coclass, double* ll, double* resp, bool miss = false);

@@ -1,8 +1,8 @@
 // summary_launch.hpp -- launchers of the posterior-summary kernels: posterior.hip
 // (launch_psm, launch_vi_terms), trace_summary.hip (launch_tr_pack .. launch_tr_reduce,
 // launch_tg_*) and trace_uncertainty.hip (launch_tr_transpose, launch_tr_affinity,
-// launch_tr_cross), trace_refine.hip (launch_rf_htable, launch_rf_gains) and predict.hip
-// (launch_pr_new .. launch_pr_impute).  Included by the units that
+// launch_tr_cross), trace_refine.hip (launch_rf_htable, launch_rf_gains), predict.hip
+// (launch_pr_new .. launch_pr_impute) and profile.hip (launch_pf_*).  Included by the units that
 // define them and by summary_host.cpp, their only caller.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -124,5 +124,47 @@ hipError_t launch_pr_own(const PrOwnArgs& a, hipStream_t s);
 hipError_t launch_pr_part(const PrPartArgs& a, hipStream_t s);
 hipError_t launch_pr_exp(const double* x, int64_t n, double* out, hipStream_t s);
 hipError_t launch_pr_impute(const PrImpArgs& a, hipStream_t s);
+
+// profile.hip.  The estimate's tables tab = T^s[a][k] at tab[(s * Ka + a) * Kz + k] (k_tr_tables)
+// folded with the parameter tables above; sig holds the raw sigmas, rows of d.
+constexpr int kPfThreads = 256;     // lanes of k_pf_sigma over the attributes of one (draw, class)
+// k_pf_sigma: u_s of the draws s0 .. s1 - 1, u[((s - s0) * Ka + a) * d + j]
+struct PfSigArgs {
+  const uint32_t* tab;
+  int Ka, Kz, d, s0, s1;
+  const int64_t* off;
+  const double* sig;
+  const double* na;                 // Ka class sizes
+  double* u;
+};
+// k_pf_welford: the chunk's u_s folded into (mean, m2) per (class, attribute), st[0 .. n) the
+// means and st[n .. 2n) the m2, n = Ka x d; at the last chunk mean / var receive the results
+struct PfWelArgs {
+  const double* u;
+  int n, s0, s1, M;
+  double* st;
+  double* mean;                     // n each, or null
+  double* var;
+};
+// k_pf_levels: the level rows of the attributes j0 .. j0 + jb - 1 over all the draws, staged as
+// (a * jb + j - j0) * ld + l - 1, every slot written; cnt and law may each be null.  A lane keeps
+// its level rows in LDS during the walk: kPfLdsBytes per workgroup (one wave) bound the lanes
+// that work (launch_pf_levels sets `lanes`)
+constexpr int kPfLdsBytes = 64 << 10;
+constexpr int kPfGroup = 4;         // clusters whose parameters a lane fetches together
+struct PfLevArgs {
+  const uint32_t* tab;
+  int M, Ka, Kz, d, j0, jb, ld, lanes;
+  const int64_t* off;
+  const uint8_t* cen;
+  const double* emm;
+  const int32_t* att;
+  const double* na;
+  uint64_t* cnt;
+  double* law;
+};
+hipError_t launch_pf_sigma(const PfSigArgs& a, hipStream_t s);
+hipError_t launch_pf_welford(const PfWelArgs& a, hipStream_t s);
+hipError_t launch_pf_levels(const PfLevArgs& a, hipStream_t s);
 
 }  // namespace hdpm

@@ -24,7 +24,9 @@ the expected VI or Binder's loss until no move helps (csrc/trace_refine.hip;
 sigmas beside the labels (csrc/predict.hip through ``hdpm_predict_*``): the posterior
 predictive of rows the chain never saw -- their density, their class of a point estimate, the
 probability of a cluster of their own -- and the pointwise log-likelihood of the training rows
-behind ``waic`` and ``lpml``.  ``arandi``, ``ess`` and ``iat`` are
+behind ``waic`` and ``lpml``; ``Predictive.profile`` (csrc/profile.hip) says what each class of
+an estimate is, the posterior law of its center codes and its sigmas with their spread, with no
+matching of labels between draws.  ``arandi``, ``ess`` and ``iat`` are
 restated on the host.  None of these packages is installed here (no R), so their parity is
 unpinned; ``arandi`` is checked against scikit-learn's adjusted Rand score.
 """
@@ -446,6 +448,49 @@ class Predictive:
                                               ptr(pmf) if rows.size else None, ptr(lpd)))
         mode = np.argmax(pmf, axis=1) + 1 if rows.size and ld else np.zeros(rows.size, np.int64)
         return rows, attrs, pmf, mode, lpd
+
+    def profile(self, cl, Ka: int | None = None, ld: int | None = None, trace: bool = False) -> dict:
+        """What each class of the partition ``cl`` is (csrc/profile.hip; ``cl`` and ``Ka`` as in
+        ``classify``): per class a and attribute j, the posterior law of the center code and the
+        sigma of the members of a.  A member i takes its draw's parameters, those of its cluster
+        z_s(i), so the averages over members and draws need no matching of labels between draws.
+        ``ld`` is the number of level slots (default the largest attrisize).  Keys:
+
+        "center_cnt" (Ka x d x ld uint64, exact) and "center_pmf" = center_cnt / (M n_a): the
+        posterior probability that the center of a member of a has code l at attribute j;
+        "mode" (Ka x d: the first arg-max level, 1-based, 0 for an empty class) and "mode_prob";
+        "code_pmf" (Ka x d x ld): the model's predictive law of a member's code, to hold against
+        the class's observed code frequencies; "sigma_mean" and "sigma_sd" (Ka x d): the mean and
+        the standard deviation (ddof 1; 0 when M = 1) over the draws of the members' mean sigma;
+        "sigma_trace" (M x Ka x d, only with ``trace``): that mean per draw, the relabelled
+        parameter trace for quantiles, trace plots and ``ess``; "sizes" (Ka).  An empty class
+        has 0 everywhere."""
+        eng = self.trace.eng
+        if Ka is None:
+            c = self.trace._one(cl)[0]
+            Ka = int(c.max()) + 1
+        else:
+            c = np.ascontiguousarray(cl, dtype=np.int32).ravel()
+            if c.size != self.N:
+                raise ValueError("the partition must have N labels")
+        Ka = int(Ka)
+        ld = int(self.att.max()) if ld is None else int(ld)
+        shape = (max(Ka, 0), self.d, max(ld, 0))
+        cnt, pmf = np.zeros(shape, np.uint64), np.zeros(shape)
+        mean, var = np.zeros(shape[:2]), np.zeros(shape[:2])
+        tr = np.zeros((self.M,) + shape[:2]) if trace else None
+        eng._check(eng._L.hdpm_predict_profile(eng._h, ptr(c), Ka, ld, ptr(cnt), ptr(pmf), ptr(mean), ptr(var),
+                                               ptr(tr)))
+        sizes = np.bincount(c, minlength=Ka).astype(np.int64)
+        den = (self.M * sizes).astype(np.float64)[:, None, None]
+        cpmf = np.zeros(shape)
+        np.divide(cnt, den, out=cpmf, where=den > 0)
+        mode = np.where(sizes[:, None] > 0, np.argmax(cnt, axis=2) + 1, 0)
+        out = {"center_cnt": cnt, "center_pmf": cpmf, "mode": mode, "mode_prob": cpmf.max(axis=2), "code_pmf": pmf,
+               "sigma_mean": mean, "sigma_sd": np.sqrt(var), "sizes": sizes}
+        if trace:
+            out["sigma_trace"] = tr
+        return out
 
     def pointwise(self, X):
         """(lppd, var, logcpo) of the N training rows ``X`` (the rows the chain ran on): per
