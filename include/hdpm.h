@@ -508,7 +508,8 @@ int hdpm_trace_distances(hdpm_ctx* ctx, const int32_t* cls, int32_t ncand, doubl
                          int32_t* draw_k);
 int hdpm_trace_affinity(hdpm_ctx* ctx, const int32_t* cl, int32_t Ka, uint64_t* aff, uint64_t* cross);
 /* A point estimate refined by single-point moves (the local search of mcclust.ext's greedy and
- * of SALSO, without their merges, splits and restarts), after hdpm_trace_build and with
+ * of SALSO, without their splits and restarts; their merges are hdpm_trace_refine_merge's,
+ * below: hdpm_trace_refine itself makes none), after hdpm_trace_build and with
  * hdpm_trace_affinity's refusals; an unknown loss or a negative max_rounds is HDPM_E_ARG too.
  * With n_a the class sizes of cl, T^m its table against draw z_m and
  *   h(t) = (t + 1) log2(t + 1) - t log2 t, h(0) = 0, evaluated as
@@ -559,6 +560,58 @@ int hdpm_trace_move_gains(hdpm_ctx* ctx, const int32_t* cl, int32_t Ka, int32_t 
                           double* full);
 int hdpm_trace_refine(hdpm_ctx* ctx, const int32_t* cl, int32_t loss, int32_t max_rounds, int32_t* cl_out,
                       hdpm_refine_info* info, double* history);
+/* Merges of two classes as moves: a descent by single-point moves stalls where the draws leave
+ * open whether two classes are one (every point is more similar to its own half), and merging
+ * the classes lowers the loss.  The gains of all pairs are functions of the tables T^m and the
+ * class sizes alone: one table pass, whatever the number of pairs.  After hdpm_trace_build and
+ * with hdpm_trace_affinity's refusals (a label >= Ka, Ka outside 1..255); an unknown loss is
+ * HDPM_E_ARG, and HDPM_LOSS_BINDER needs N^2 M < 2^63.  With
+ *   f(s, t) = (s + t) log2(s + t) - s log2 s - t log2 t for s, t >= 1 and 0 if s = 0 or t = 0,
+ *             evaluated as (s log1p(t / s) + t log1p(s / t)) / ln 2,
+ * merging the non-empty classes a < b of cl changes the loss by
+ *   HDPM_LOSS_VI:     mgain[a][b] = (M f(n_a, n_b) - 2 sum_m sum_z f(T^m[a][z], T^m[b][z])) / (M N),
+ *                     the change of hdpm_trace_losses' vi.  The sum runs over 64 slices of the
+ *                     draws (m = y, y + 64, ..; M slices if M < 64), within a slice in draw order
+ *                     and z ascending, and the slices are added in order: no value depends on
+ *                     table_budget_bytes or on Ka;
+ *   HDPM_LOSS_BINDER: mgain[a][b] = M n_a n_b - 2 cross[a][b] (hdpm_trace_affinity's cross), the
+ *                     exact change of the integer M A + P - 2 Q, formed in 64 bits and returned as
+ *                     a double that holds it (|gain| <= 3 M N^2).
+ * The matrix is symmetric with a zero diagonal, and a pair with an empty class has gain exactly 0.
+ *
+ * hdpm_trace_merge_gains: gain[a * Ka + b] = mgain[a][b] (Ka x Ka); best[2] the pair a < b of
+ *   non-empty classes with the smallest gain, the lowest a winning a tie and then the lowest b,
+ *   and *best_gain its gain; with fewer than two non-empty classes best = {-1, -1} and
+ *   *best_gain = 0.  An empty class is never a candidate.  Any output may be NULL.
+ * hdpm_trace_merge_path: greedy agglomeration from cl (labels 0..Ka-1 as they stand) down to
+ *   k_min classes (k_min >= 1, HDPM_E_ARG otherwise).  *steps = max(0, K0 - k_min) with K0 the
+ *   non-empty classes of cl.  Each step merges the best pair (the rule above) of the current
+ *   state, whether or not its gain is negative; the merged class keeps the lower label a, and
+ *   merge[2 s], merge[2 s + 1] = a, b name the caller's labels.  step_gain[s] is that pair's
+ *   gain.  value[0] is the loss of cl and value[s + 1] the loss after step s, evaluated from the
+ *   merged tables (row b of every T^m added into row a) and never as the running sum of the
+ *   gains: VI as hdpm_trace_losses' vi, Binder's integer M A + P - 2 Q exactly, as a double.
+ *   One pass over the points runs at the start; every step works on the tables alone.  merge
+ *   holds up to (Ka - 1) x 2 entries, step_gain Ka - 1, value Ka.  Any output may be NULL.
+ * hdpm_trace_refine_merge: alternates two phases from cl (labels 0..254).  The descent of
+ *   hdpm_trace_refine, with the rounds left of max_rounds, ends at c with loss L; if it ran out
+ *   of rounds with candidates left the run stops with converged = 0.  Otherwise the pair gains
+ *   of c are taken: no pair with gain < 0 stops the run with converged = 1 (c is a minimum
+ *   under single-point moves and pair merges); after max_merges accepted merges a negative pair
+ *   stops it with converged = 0.  Else the best pair is tried: the merged partition relabelled
+ *   by first appearance, its loss evaluated as every trial of hdpm_trace_refine is, accepted
+ *   iff strictly below L.  A rejected merge stops the run with converged = 1 (VI only, by
+ *   rounding); an accepted one is followed by the descent again.  Every accepted step lowers the
+ *   evaluated loss strictly, so the run ends.  info covers the whole run (trials counts the
+ *   evaluated trials of both phases), *merges the accepted merges, and history[max_rounds +
+ *   max_merges + 1] (may be NULL) holds the loss at the start and after each accepted round or
+ *   merge, info->rounds + *merges + 1 values.  A negative max_rounds or max_merges is HDPM_E_ARG. */
+int hdpm_trace_merge_gains(hdpm_ctx* ctx, const int32_t* cl, int32_t Ka, int32_t loss, double* gain, int32_t* best,
+                           double* best_gain);
+int hdpm_trace_merge_path(hdpm_ctx* ctx, const int32_t* cl, int32_t Ka, int32_t loss, int32_t k_min, int32_t* merge,
+                          double* step_gain, double* value, int32_t* steps);
+int hdpm_trace_refine_merge(hdpm_ctx* ctx, const int32_t* cl, int32_t loss, int32_t max_rounds, int32_t max_merges,
+                            int32_t* cl_out, hdpm_refine_info* info, int32_t* merges, double* history);
 /* mcclust.ext minVI(method = "avg") / mcclust minbinder(method = "avgl") =
  * hclust(as.dist(1 - psm), "average") + cutree, from the saved labels alone.  Points whose
  * labels agree in every draw have psm = 1 (distance 0) and any other pair has distance

@@ -5,8 +5,9 @@ kernels and the host runtime live in ``libhdpm.so`` (C ABI: include/hdpm.h); thi
 package is the Python mirror of the reference interface.
 """
 from ._lib import HdpmError, build  # noqa: F401
-from .posterior import LabelTrace, Predictive, credible_ball, lpml, minbinder, refine, waic  # noqa: F401
+from .posterior import (LabelTrace, Predictive, coarsen, credible_ball, lpml, minbinder, refine,  # noqa: F401
+                        waic)
 from .sampler import Debug, Engine, run_markov_chain  # noqa: F401
 
 __all__ = ["Engine", "Debug", "run_markov_chain", "HdpmError", "build", "LabelTrace", "minbinder", "credible_ball",
-           "Predictive", "waic", "lpml", "refine"]
+           "Predictive", "waic", "lpml", "refine", "coarsen"]

@@ -33,6 +33,7 @@ EXPORTS = (
     "hdpm_trace_groups", "hdpm_trace_group_info", "hdpm_trace_avg_tree", "hdpm_trace_cut_losses",
     "hdpm_trace_cut_labels", "hdpm_trace_distances", "hdpm_trace_affinity", "hdpm_sm_last_terms",
     "hdpm_trace_move_gains", "hdpm_trace_refine",
+    "hdpm_trace_merge_gains", "hdpm_trace_merge_path", "hdpm_trace_refine_merge",
     "hdpm_predict_build", "hdpm_predict_new", "hdpm_predict_own", "hdpm_predict_loglik",
     "hdpm_predict_partial", "hdpm_predict_impute", "hdpm_predict_profile",
     "hdpm_debug_launches",
@@ -243,6 +244,9 @@ def lib():
         "hdpm_trace_affinity": ([vp, vp, i32, vp, vp], C.c_int),
         "hdpm_trace_move_gains": ([vp, vp, i32, i32, vp, vp, vp], C.c_int),
         "hdpm_trace_refine": ([vp, vp, i32, i32, vp, P(RefineInfo), vp], C.c_int),
+        "hdpm_trace_merge_gains": ([vp, vp, i32, i32, vp, vp, vp], C.c_int),
+        "hdpm_trace_merge_path": ([vp, vp, i32, i32, i32, vp, vp, vp, vp], C.c_int),
+        "hdpm_trace_refine_merge": ([vp, vp, i32, i32, i32, vp, P(RefineInfo), vp, vp], C.c_int),
         "hdpm_predict_build": ([vp, i32, vp, f64, vp, vp, vp], C.c_int),
         "hdpm_predict_new": ([vp, vp, i32, vp, i32, vp, vp, vp], C.c_int),
         "hdpm_predict_own": ([vp, vp, vp, vp, vp], C.c_int),

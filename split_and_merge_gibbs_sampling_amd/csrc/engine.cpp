@@ -5567,6 +5567,21 @@ int hdpm_trace_refine(hdpm_ctx* h, const int32_t* cl, int32_t loss, int32_t max_
   CTX();
   GUARD(return ctx->sum.trace_refine(cl, loss, max_rounds, cl_out, info, history);)
 }
+int hdpm_trace_merge_gains(hdpm_ctx* h, const int32_t* cl, int32_t Ka, int32_t loss, double* gain, int32_t* best,
+                           double* best_gain) {
+  CTX();
+  GUARD(return ctx->sum.trace_merge_gains(cl, Ka, loss, gain, best, best_gain);)
+}
+int hdpm_trace_merge_path(hdpm_ctx* h, const int32_t* cl, int32_t Ka, int32_t loss, int32_t k_min, int32_t* merge,
+                          double* step_gain, double* value, int32_t* steps) {
+  CTX();
+  GUARD(return ctx->sum.trace_merge_path(cl, Ka, loss, k_min, merge, step_gain, value, steps);)
+}
+int hdpm_trace_refine_merge(hdpm_ctx* h, const int32_t* cl, int32_t loss, int32_t max_rounds, int32_t max_merges,
+                            int32_t* cl_out, hdpm_refine_info* info, int32_t* merges, double* history) {
+  CTX();
+  GUARD(return ctx->sum.trace_refine_merge(cl, loss, max_rounds, max_merges, cl_out, info, merges, history);)
+}
 int hdpm_trace_groups(hdpm_ctx* h, int32_t max_groups, int32_t hash_bits, int32_t* U_out) {
   CTX();
   GUARD(return ctx->sum.trace_groups(max_groups, hash_bits, U_out);)

@@ -1,7 +1,8 @@
 // summary_host.cpp -- host side of the posterior summaries (summary_host.hpp): the dense
 // psm of posterior.hip, the matrix-free summaries of trace_summary.hip, the uncertainty
 // calls of trace_uncertainty.hip, the single-point moves of trace_refine.hip (their descent
-// rule is in trace_refine.hpp), the average-linkage search of trace_tree.hpp and the
+// rule is in trace_refine.hpp), the pair merges of trace_merge.hip (their rules are in
+// trace_merge.hpp), the average-linkage search of trace_tree.hpp and the
 // posterior predictive of predict.hip with the class profiles of profile.hip.  The arithmetic
 // that turns the device's integer sums into losses is in trace_loss.hpp, that of the
 // predictive's tables and checks in predict_host.hpp, the profiles' checks and cuts in
@@ -18,6 +19,7 @@
 #include "profile_host.hpp"
 #include "summary_launch.hpp"
 #include "trace_loss.hpp"
+#include "trace_merge.hpp"
 #include "trace_refine.hpp"
 #include "trace_tree.hpp"
 
@@ -464,6 +466,27 @@ int Summaries::trace_move_gains(const int32_t* cl, int32_t Ka, int32_t loss, int
   if (best || gain || full) move_gains(cl, Ka, loss, best, gain, full);
   return HDPM_OK;
 }
+// the loss of one partition (labels 0..K-1) as the descents compare it: hdpm_trace_losses' vi,
+// and Binder's integer M A + P - 2 Q
+double Summaries::vi_of(const int32_t* c, int K) {
+  double v = 0.0;
+  losses({c, 0, 1}, K, nullptr, &v, nullptr, nullptr);
+  return v;
+}
+uint64_t Summaries::binder_of(const int32_t* c, int K) {
+  uint64_t A = 0, Q = 0;
+  losses({c, 0, 1}, K, nullptr, nullptr, &A, &Q);
+  return (uint64_t)tr_M * A + tr_P - 2 * Q;
+}
+static void rf_export(const RfInfo& r, hdpm_refine_info* info) {
+  info->rounds = r.rounds;
+  info->trials = r.trials;
+  info->converged = r.converged;
+  info->K = r.K;
+  info->moved = r.moved;
+  info->start = r.start;
+  info->value = r.value;
+}
 int Summaries::trace_refine(const int32_t* cl, int32_t loss, int32_t max_rounds, int32_t* cl_out,
                             hdpm_refine_info* info, double* history) {
   int used = 0;
@@ -479,27 +502,134 @@ int Summaries::trace_refine(const int32_t* cl, int32_t loss, int32_t max_rounds,
   };
   RfInfo r;
   if (loss == HDPM_LOSS_VI) {
-    rf_run<double>(cl, tr_N, max_rounds, gains, [&](const int32_t* c, int K) {
-      double v = 0.0;
-      losses({c, 0, 1}, K, nullptr, &v, nullptr, nullptr);
-      return v;
-    }, cl_out, &r, history);
+    rf_run<double>(cl, tr_N, max_rounds, gains, [&](const int32_t* c, int K) { return vi_of(c, K); }, cl_out, &r,
+                   history);
   } else {
-    rf_run<uint64_t>(cl, tr_N, max_rounds, gains, [&](const int32_t* c, int K) {
-      uint64_t A = 0, Q = 0;
-      losses({c, 0, 1}, K, nullptr, nullptr, &A, &Q);
-      return (uint64_t)tr_M * A + tr_P - 2 * Q;
-    }, cl_out, &r, history);
+    rf_run<uint64_t>(cl, tr_N, max_rounds, gains, [&](const int32_t* c, int K) { return binder_of(c, K); }, cl_out,
+                     &r, history);
   }
-  if (info) {
-    info->rounds = r.rounds;
-    info->trials = r.trials;
-    info->converged = r.converged;
-    info->K = r.K;
-    info->moved = r.moved;
-    info->start = r.start;
-    info->value = r.value;
+  if (info) rf_export(r, info);
+  return HDPM_OK;
+}
+
+// ---- pair merges (trace_merge.hip, trace_merge.hpp)
+// what hdpm_trace_affinity refuses, an unknown loss, and Binder's 63-bit bound
+int Summaries::check_one(const int32_t* cl, int32_t Ka, int32_t loss) {
+  int used = 0;   // the largest label + 1
+  if (int st = check(cl, 1, &used)) return st;
+  if (Ka < 1 || Ka > 255) { err = "trace: Ka must be in 1..255"; return HDPM_E_ARG; }
+  if (used > Ka) { err = "trace: the partition's labels must be in 0..Ka-1"; return HDPM_E_ARG; }
+  if (loss != HDPM_LOSS_VI && loss != HDPM_LOSS_BINDER) { err = "trace: unknown loss"; return HDPM_E_ARG; }
+  if (loss == HDPM_LOSS_BINDER && !tl_fits63((uint64_t)tr_N, (uint64_t)tr_M)) {
+    err = "trace: N^2 M does not fit 63 bits: Binder's integer would overflow";
+    return HDPM_E_ARG;
   }
+  return HDPM_OK;
+}
+// the tables of the one candidate stand in d_tr_tab: their transpose, and the class sizes
+void Summaries::merge_setup(const uint8_t* rows, int Ka, std::vector<uint64_t>& sz) {
+  sz.assign((size_t)Ka, 0);
+  for (int i = 0; i < tr_N; ++i) sz[rows[i]]++;
+  d_tr_tabT.ensure((size_t)tr_M * Ka * tr_Kz);
+  HIPCHK(launch_tr_transpose(d_tr_tab.p, tr_M, Ka, tr_Kz, d_tr_tabT.p, stream));
+}
+// the Ka x Ka gains of the tables in d_tr_tabT with class sizes sz, to the host.  only >= 0:
+// VI's partial sums of the last call stand, and only the pairs of that class are taken again
+void Summaries::merge_gains(int loss, int Ka, int only, const std::vector<uint64_t>& sz, double* gain) {
+  const int M = tr_M, Kz = tr_Kz;
+  const size_t KK = (size_t)Ka * Ka;
+  std::vector<double> n(sz.begin(), sz.end());
+  d_mg_n.ensure((size_t)Ka);
+  d_mg_gain.ensure(KK);
+  HIPCHK(hipMemcpyAsync(d_mg_n.p, n.data(), (size_t)Ka * 8, hipMemcpyHostToDevice, stream));
+  if (loss == HDPM_LOSS_VI) {
+    d_mg_part.ensure((size_t)mg_slices(M) * KK);
+    HIPCHK(launch_mg_pairs(d_tr_tabT.p, M, Ka, Kz, only, d_mg_part.p, stream));
+  } else {
+    d_tr_cross.ensure(KK);
+    HIPCHK(hipMemsetAsync(d_tr_cross.p, 0, KK * 8, stream));
+    HIPCHK(launch_tr_cross(d_tr_tabT.p, M, Ka, Kz, d_tr_cross.p, stream));
+  }
+  HIPCHK(launch_mg_gain(loss, d_mg_part.p, d_tr_cross.p, d_mg_n.p, M, Ka, tr_N, d_mg_gain.p, stream));
+  HIPCHK(hipMemcpyAsync(gain, d_mg_gain.p, KK * 8, hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipStreamSynchronize(stream));
+}
+int Summaries::trace_merge_gains(const int32_t* cl, int32_t Ka, int32_t loss, double* gain, int32_t* best,
+                                 double* best_gain) {
+  if (int st = check_one(cl, Ka, loss)) return st;
+  if (!gain && !best && !best_gain) return HDPM_OK;
+  std::vector<double> g((size_t)Ka * Ka);
+  std::vector<uint64_t> sz;
+  blocks({cl, 0, 1}, Ka, false, false, false, [&](int, int, const uint8_t* rows) {
+    merge_setup(rows, Ka, sz);
+    merge_gains(loss, Ka, -1, sz, g.data());
+  });
+  const MgPair p = mg_best(g.data(), sz.data(), Ka);
+  if (gain) std::copy(g.begin(), g.end(), gain);
+  if (best) { best[0] = p.a; best[1] = p.b; }
+  if (best_gain) *best_gain = p.gain;
+  return HDPM_OK;
+}
+int Summaries::trace_merge_path(const int32_t* cl, int32_t Ka, int32_t loss, int32_t k_min, int32_t* merge,
+                                double* step_gain, double* value, int32_t* steps) {
+  if (int st = check_one(cl, Ka, loss)) return st;
+  if (k_min < 1) { err = "trace: merge_path needs k_min >= 1"; return HDPM_E_ARG; }
+  const int M = tr_M, N = tr_N, Kz = tr_Kz;
+  int nsteps = 0;
+  std::vector<uint64_t> sz;
+  std::vector<double> lsz((size_t)Ka);
+  // one table pass; then folds, pair gains and the reductions of the folded tables
+  blocks({cl, 0, 1}, Ka, false, false, false, [&](int, int, const uint8_t* rows) {
+    merge_setup(rows, Ka, sz);
+    auto loss_now = [&]() {
+      uint64_t q = 0;
+      double l = 0.0;
+      HIPCHK(launch_tr_reduce(d_tr_tab.p, 1, M, Ka * Kz, d_tr_q1.p, d_tr_l1.p, d_tr_q.p, d_tr_l.p, stream));
+      HIPCHK(hipMemcpyAsync(&q, d_tr_q.p, 8, hipMemcpyDeviceToHost, stream));
+      HIPCHK(hipMemcpyAsync(&l, d_tr_l.p, 8, hipMemcpyDeviceToHost, stream));
+      HIPCHK(hipStreamSynchronize(stream));
+      const TlSizes s = tl_sizes(sz.data(), Ka, lsz.data());
+      return loss == HDPM_LOSS_VI ? tl_vi(s.hc, tr_S, l, (double)M, N) : (double)((uint64_t)M * s.A + tr_P - 2 * q);
+    };
+    nsteps = mg_path(
+        sz.data(), Ka, k_min, [&](int changed, double* g) { merge_gains(loss, Ka, changed, sz, g); },
+        [&](int a, int b) { HIPCHK(launch_mg_fold(d_tr_tab.p, d_tr_tabT.p, M, Ka, Kz, a, b, stream)); }, loss_now, merge,
+        step_gain, value);
+  });
+  if (steps) *steps = nsteps;
+  return HDPM_OK;
+}
+int Summaries::trace_refine_merge(const int32_t* cl, int32_t loss, int32_t max_rounds, int32_t max_merges,
+                                  int32_t* cl_out, hdpm_refine_info* info, int32_t* merges, double* history) {
+  int used = 0;
+  if (int st = check(cl, 1, &used)) return st;
+  if (int st = check_one(cl, used, loss)) return st;
+  if (max_rounds < 0 || max_merges < 0 || !cl_out) {
+    err = "trace: refine_merge needs max_rounds >= 0, max_merges >= 0 and cl_out";
+    return HDPM_E_ARG;
+  }
+  auto gains = [&](const int32_t* c, int K, int32_t* best, double* gain) {
+    move_gains(c, K, loss, best, gain, nullptr);
+  };
+  std::vector<double> g;
+  std::vector<uint64_t> sz;
+  auto pairs = [&](const int32_t* c, int K) {
+    g.resize((size_t)K * K);
+    blocks({c, 0, 1}, K, false, false, false, [&](int, int, const uint8_t* rows) {
+      merge_setup(rows, K, sz);
+      merge_gains(loss, K, -1, sz, g.data());
+    });
+    return mg_best(g.data(), sz.data(), K);
+  };
+  RfInfo r;
+  if (loss == HDPM_LOSS_VI) {
+    mg_run<double>(cl, tr_N, max_rounds, max_merges, gains, [&](const int32_t* c, int K) { return vi_of(c, K); },
+                   pairs, cl_out, &r, merges, history);
+  } else {
+    mg_run<uint64_t>(cl, tr_N, max_rounds, max_merges, gains,
+                     [&](const int32_t* c, int K) { return binder_of(c, K); }, pairs, cl_out, &r, merges, history);
+  }
+  if (info) rf_export(r, info);
   return HDPM_OK;
 }
 

@@ -35,6 +35,11 @@ class Summaries {
   int trace_move_gains(const int32_t* cl, int32_t Ka, int32_t loss, int32_t* best, double* gain, double* full);
   int trace_refine(const int32_t* cl, int32_t loss, int32_t max_rounds, int32_t* cl_out, hdpm_refine_info* info,
                    double* history);
+  int trace_merge_gains(const int32_t* cl, int32_t Ka, int32_t loss, double* gain, int32_t* best, double* best_gain);
+  int trace_merge_path(const int32_t* cl, int32_t Ka, int32_t loss, int32_t k_min, int32_t* merge, double* step_gain,
+                       double* value, int32_t* steps);
+  int trace_refine_merge(const int32_t* cl, int32_t loss, int32_t max_rounds, int32_t max_merges, int32_t* cl_out,
+                         hdpm_refine_info* info, int32_t* merges, double* history);
   int trace_groups(int32_t max_groups, int32_t hash_bits, int32_t* U_out);
   int trace_group_info(int32_t* first, int32_t* weight, int32_t* group_of, uint32_t* counts);
   int trace_avg_tree(int32_t* merge, double* height);
@@ -86,6 +91,9 @@ class Summaries {
   DevBuf<double> d_rf_h, d_rf_ct, d_rf_gain;
   DevBuf<uint64_t> d_rf_stage;
   DevBuf<int32_t> d_rf_best;
+  // the pair merges (trace_merge.hip): VI's per-slice partial sums (slices x Ka x Ka), the class
+  // sizes and the Ka x Ka gains; Binder reads d_tr_cross
+  DevBuf<double> d_mg_part, d_mg_n, d_mg_gain;
   // groups of equal label columns and their average-linkage tree (trace_groups ..
   // trace_cut_labels): the open-addressing table, group_of per point, the groups'
   // signatures both ways round, S (U x U) once it is first needed, the tree on the host
@@ -136,6 +144,11 @@ class Summaries {
   void blocks(Cands cd, int Ka, bool terms, bool want_all, bool reduce, F f);
   void losses(Cands cd, int Ka, double* vi_lb, double* vi, uint64_t* binder_A, uint64_t* binder_Q);
   void move_gains(const int32_t* cl, int Ka, int loss, int32_t* best, double* gain, double* full);
+  double vi_of(const int32_t* c, int K);
+  uint64_t binder_of(const int32_t* c, int K);
+  int check_one(const int32_t* cl, int32_t Ka, int32_t loss);
+  void merge_setup(const uint8_t* rows, int Ka, std::vector<uint64_t>& sz);
+  void merge_gains(int loss, int Ka, int only, const std::vector<uint64_t>& sz, double* gain);
   void group_counts();
 };
 

@@ -1,7 +1,8 @@
 // summary_launch.hpp -- launchers of the posterior-summary kernels: posterior.hip
 // (launch_psm, launch_vi_terms), trace_summary.hip (launch_tr_pack .. launch_tr_reduce,
 // launch_tg_*) and trace_uncertainty.hip (launch_tr_transpose, launch_tr_affinity,
-// launch_tr_cross), trace_refine.hip (launch_rf_htable, launch_rf_gains), predict.hip
+// launch_tr_cross), trace_refine.hip (launch_rf_htable, launch_rf_gains), trace_merge.hip
+// (launch_mg_pairs, launch_mg_gain, launch_mg_fold), predict.hip
 // (launch_pr_new .. launch_pr_impute) and profile.hip (launch_pf_*).  Included by the units that
 // define them and by summary_host.cpp, their only caller.
 #pragma once
@@ -34,6 +35,16 @@ hipError_t launch_rf_htable(const uint32_t* tab, int M, int Ka, int Kz, double* 
 hipError_t launch_rf_gains(int loss, const uint8_t* lab, const uint8_t* cls, int Np, int M, int Ka, int Kz,
                            const void* tabT, int i0, int npts, const double* ct, int N, int full, uint64_t* stage,
                            int32_t* best, double* gain, hipStream_t s);
+// trace_merge.hip.  launch_mg_pairs: VI's per-slice partial sums of all pairs (only < 0) or of the
+// pairs of class `only`, into part (mg_slices(M) x Ka x Ka doubles).  launch_mg_gain: the Ka x Ka
+// gains from part (HDPM_LOSS_VI) or from launch_tr_cross's integers (HDPM_LOSS_BINDER) and the
+// class sizes n (Ka doubles).  launch_mg_fold: row b of every draw's table added into row a
+// and zeroed, in tab (M x Ka x Kz) and tabT (M x Kz x Ka); either may be null.
+int mg_slices(int M);
+hipError_t launch_mg_pairs(const uint32_t* tabT, int M, int Ka, int Kz, int only, double* part, hipStream_t s);
+hipError_t launch_mg_gain(int loss, const double* part, const uint64_t* cross, const double* n, int M, int Ka, int N,
+                          double* gain, hipStream_t s);
+hipError_t launch_mg_fold(uint32_t* tab, uint32_t* tabT, int M, int Ka, int Kz, int a, int b, hipStream_t s);
 hipError_t launch_tg_insert(const uint8_t* lab, int N, int Np, int M, int hash_bits, uint32_t tslots,
                             uint32_t max_groups, uint32_t* rep, uint32_t* first, uint32_t* pslot, uint32_t* ctl,
                             hipStream_t s);

@@ -20,7 +20,10 @@ labels agree in every draw, again with no matrix.  ``credible_ball`` (mcclust.ex
 script's PSM plot ordered by ``VI$cl``) say how far that estimate can be trusted, from the
 same tables (csrc/trace_uncertainty.hip), and ``refine`` improves it by single-point moves on
 the expected VI or Binder's loss until no move helps (csrc/trace_refine.hip;
-``LabelTrace.move_gains`` gives every point's best move).  ``Predictive`` reads the recorded centers and
+``LabelTrace.move_gains`` gives every point's best move) and, with ``merges``, by merging two
+classes where single moves stall (csrc/trace_merge.hip; ``LabelTrace.merge_gains`` gives every
+pair's gain, ``LabelTrace.merge_path`` with ``coarsen`` the greedy agglomeration and the loss of
+each of its levels).  ``Predictive`` reads the recorded centers and
 sigmas beside the labels (csrc/predict.hip through ``hdpm_predict_*``): the posterior
 predictive of rows the chain never saw -- their density, their class of a point estimate, the
 probability of a cluster of their own -- and the pointwise log-likelihood of the training rows
@@ -300,6 +303,53 @@ class LabelTrace:
                                                           ptr(gains)))
         return (best, gain, gains) if full else (best, gain)
 
+    # ---- pair merges (csrc/trace_merge.hip)
+
+    def _as_given(self, cl, Ka):
+        """(labels, Ka): relabelled 0..Ka-1 as the candidates are, or, with ``Ka`` given, the
+        labels 0..Ka-1 as they stand"""
+        if Ka is None:
+            c = self._one(cl)[0]
+            return c, int(c.max()) + 1
+        c = np.ascontiguousarray(cl, dtype=np.int32).ravel()
+        if c.size != self.N:
+            raise ValueError("the partition must have N labels")
+        return c, int(Ka)
+
+    def merge_gains(self, cl, loss: str = "VI", Ka: int | None = None):
+        """(gain, best, best_gain): what merging two classes of ``cl`` (relabelled 0..Ka-1 as the
+        candidates are; with ``Ka`` given, labels 0..Ka-1 as they stand, so a class may be empty)
+        would change in ``loss``: "VI", the change of ``vi``, or "Binder", the change of the
+        exact integer M A + P - 2 Q (M times ``binder``), as a double that holds it.  gain is
+        Ka x Ka, symmetric, 0 on the diagonal and for a pair with an empty class; best is the
+        pair a < b of non-empty classes with the smallest gain (the lowest a wins a tie, then the
+        lowest b), (-1, -1) with gain 0 if there are fewer than two.  One table pass, whatever
+        the number of pairs."""
+        code = _loss_code(loss)
+        c, Ka = self._as_given(cl, Ka)
+        gain = np.zeros((max(Ka, 0), max(Ka, 0)))
+        best, bg = np.zeros(2, np.int32), np.zeros(1)
+        self.eng._check(self.eng._L.hdpm_trace_merge_gains(self.eng._h, ptr(c), Ka, code, ptr(gain), ptr(best),
+                                                           ptr(bg)))
+        return gain, (int(best[0]), int(best[1])), float(bg[0])
+
+    def merge_path(self, cl, loss: str = "VI", k_min: int = 1, Ka: int | None = None) -> dict:
+        """Greedy agglomeration of the classes of ``cl`` (labels as in ``merge_gains``) down to
+        ``k_min`` classes: each step merges the pair with the smallest gain, negative or not, and
+        the merged class keeps the lower label.  Returns {"merge" (steps x 2: the labels a < b of
+        each step), "step_gain" (steps), "value" (steps + 1: the loss of ``cl`` and after each
+        step, evaluated from the merged tables: ``vi``, or Binder's integer M A + P - 2 Q as a
+        double)}.  ``coarsen`` gives the labels of a level.  One pass over the points in all."""
+        code = _loss_code(loss)
+        c, Ka = self._as_given(cl, Ka)
+        rows = max(Ka - 1, 0)
+        merge, gain, value = np.zeros((rows, 2), np.int32), np.zeros(rows), np.zeros(rows + 1)
+        steps = C.c_int32(0)
+        self.eng._check(self.eng._L.hdpm_trace_merge_path(self.eng._h, ptr(c), Ka, code, int(k_min), ptr(merge),
+                                                          ptr(gain), ptr(value), C.byref(steps)))
+        s = int(steps.value)
+        return {"merge": merge[:s], "step_gain": gain[:s], "value": value[:s + 1]}
+
     # ---- the average-linkage tree without the matrix (hdpm_trace_groups .. _cut_labels)
 
     def groups(self, max_groups: int = 8192, hash_bits: int = 0) -> dict:
@@ -576,18 +626,45 @@ def _loss_code(loss: str) -> int:
     return 0 if loss == "VI" else 1       # HDPM_LOSS_VI, HDPM_LOSS_BINDER
 
 
-def refine(trace: LabelTrace, cl, loss: str = "VI", max_rounds: int = 100) -> dict:
+def coarsen(cl, merge, k: int) -> np.ndarray:
+    """The labels of ``cl`` (as ``LabelTrace.merge_path`` took them) after the first K0 - k
+    merges of ``merge``, K0 the classes of ``cl``: the path's level of k classes, relabelled
+    0..k-1 by first appearance.  Host numpy."""
+    c = np.asarray(cl).ravel().copy()
+    K0 = np.unique(c).size
+    steps = K0 - int(k)
+    merge = np.asarray(merge).reshape(-1, 2)
+    if steps < 0 or steps > merge.shape[0]:
+        raise ValueError("k must lie between K0 - len(merge) and K0")
+    for a, b in merge[:steps]:
+        c[c == b] = a
+    u, first, inv = np.unique(c, return_index=True, return_inverse=True)
+    rank = np.empty(u.size, np.int64)
+    rank[np.argsort(first)] = np.arange(u.size)
+    return rank[inv]
+
+
+def refine(trace: LabelTrace, cl, loss: str = "VI", max_rounds: int = 100, merges: int = 0) -> dict:
     """A point estimate improved by single-point moves (the local search of mcclust.ext's
-    ``greedy`` and of SALSO, without their merges, splits and restarts), with no N x N
+    ``greedy`` and of SALSO, without their splits and restarts; with ``merges`` > 0, with up
+    to that many merges of two classes), with no N x N
     matrix and no limit on the number of distinct label columns.  Each round takes every
     point's best move from ``LabelTrace.move_gains``, at most one new class among them, and
     applies the moves together, halving their number until the loss itself (``vi``, or
     Binder's exact integer) falls strictly; include/hdpm.h states the rule.  It ends at a
     partition that no single move improves (``converged``) or after ``max_rounds`` rounds.
 
+    Single moves stall where the draws leave open whether two classes are one.  With
+    ``merges`` > 0 the descent alternates with merges: at its end the pair of classes whose
+    merge lowers the loss most (``LabelTrace.merge_gains``) is merged if the evaluated loss
+    falls strictly, and the descent resumes; the run ends at a partition that neither a single
+    move nor a merge of two classes improves, or after ``merges`` merges with one still to be
+    had (``converged`` False).
+
     Returns {"cl" (1-based, labelled by first appearance), "value", "start", "rounds",
-    "trials", "moved", "converged", "history"}: history holds the loss at the start and after
-    each accepted round.  For "Binder" value and start are ``LabelTrace.binder``'s values, which
+    "trials", "moved", "converged", "history"}, and "merges" (the accepted merges) if ``merges``
+    > 0: history holds the loss at the start and after each accepted round or merge.  For
+    "Binder" value and start are ``LabelTrace.binder``'s values, which
     history begins and ends with; between them it holds the integers M A + P - 2 Q divided by
     M (the same numbers, rounded once instead of twice).  All are combined as Python ints."""
     if not isinstance(trace, LabelTrace):
@@ -595,13 +672,21 @@ def refine(trace: LabelTrace, cl, loss: str = "VI", max_rounds: int = 100) -> di
     code = _loss_code(loss)
     if max_rounds < 0:
         raise ValueError("max_rounds must be at least 0")
+    if merges < 0:
+        raise ValueError("merges must be at least 0")
     c = trace._one(cl)[0]
     out = np.zeros(trace.N, np.int32)
     info = _lib.RefineInfo()
-    hist = np.zeros(int(max_rounds) + 1)
+    hist = np.zeros(int(max_rounds) + int(merges) + 1)
     eng = trace.eng
-    eng._check(eng._L.hdpm_trace_refine(eng._h, ptr(c), code, int(max_rounds), ptr(out), C.byref(info), ptr(hist)))
-    hist = hist[:info.rounds + 1]
+    nm = C.c_int32(0)
+    if merges:
+        eng._check(eng._L.hdpm_trace_refine_merge(eng._h, ptr(c), code, int(max_rounds), int(merges), ptr(out),
+                                                  C.byref(info), C.byref(nm), ptr(hist)))
+    else:
+        eng._check(eng._L.hdpm_trace_refine(eng._h, ptr(c), code, int(max_rounds), ptr(out), C.byref(info),
+                                            ptr(hist)))
+    hist = hist[:info.rounds + nm.value + 1]
     start, value = float(info.start), float(info.value)
     if loss == "Binder":
         # the value of LabelTrace.binder, A + (P - 2 Q) / M, with P - 2 Q = (M A + P - 2 Q) - M A
@@ -611,9 +696,12 @@ def refine(trace: LabelTrace, cl, loss: str = "VI", max_rounds: int = 100) -> di
             return float(A + (int(num) - trace.M * A) / trace.M)
         start, value = binder(info.start, c), binder(info.value, out)
         hist = np.array([int(x) / trace.M for x in hist])
-        hist[0], hist[-1] = start, value if info.rounds else start
-    return {"cl": out + 1, "value": value, "start": start, "rounds": int(info.rounds), "trials": int(info.trials),
-            "moved": int(info.moved), "converged": bool(info.converged), "history": hist}
+        hist[0], hist[-1] = start, value if hist.size > 1 else start
+    r = {"cl": out + 1, "value": value, "start": start, "rounds": int(info.rounds), "trials": int(info.trials),
+         "moved": int(info.moved), "converged": bool(info.converged), "history": hist}
+    if merges:
+        r["merges"] = int(nm.value)
+    return r
 
 
 def comp_psm(c_trace, device: int = 0) -> np.ndarray:
